@@ -1,6 +1,13 @@
 """Benchmark of the self-play data-generation path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode mcts|ref] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode mcts|ref] [--dump-outputs DIR] [--full] ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs if --dump-outputs is given, and prints the result line. --full adds
+every side measurement beside the headline: the fp32 MFMA tower, the
+trained-magnitude weights, the C3-ref block (reference move selection, games
+completed), the clock held under the headline GEMM, the CPU baselines, and
+whatever --alt-precision / --f64w-steps / --compare-direct ask for.
 
 Workload (BASELINE.json configs[2], C3 -- the largest single-GPU config):
 2,048 concurrent games per GPU, 800 PUCT simulations per move, fp32 ChessNet
@@ -67,6 +74,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--mode", choices=["mcts", "ref"], default=os.environ.get("KV_BENCH_MODE", "mcts"))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (the blocks of --alt-algo, --alt-precision, --ref-block, "
+                         "--trained-steps, --f64w-steps, --compare-direct, --clock-seconds and the CPU baselines); "
+                         "without it only the headline is set up, warmed up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- its experience records "
+                         "(game id, ply, committed move, board codes) and, for MCTS, the root visit counts, ordered "
+                         "by (game id, ply) -- as DIR/<name>.npy (float32 / float64, at most 48 MiB: a fixed seeded "
+                         "sample of the rows beyond that)")
     ap.add_argument("--slots", type=int, default=2048)
     ap.add_argument("--sims", type=int, default=800)
     ap.add_argument("--precision", choices=["fp32", "f64w", "i8x5", "i8r4"], default="fp32")
@@ -117,7 +133,38 @@ def parse():
                          "reference-selection leg runs <= 10 s)")
     ap.add_argument("--cpu-leaf-batch", type=int, default=16,
                     help="games in lock-step per CPU-baseline process (their leaves as one torch batch)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline only
+        args.alt_precision = args.alt_algo = ""
+        args.ref_block = args.compare_direct = args.trained_steps = args.f64w_steps = 0
+        args.clock_seconds = 0.0
+        args.no_cpu_baseline = True
+    return args
+
+
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def dump_outputs(directory: str, recs: np.ndarray, pi):
+    """The last timed step's outputs as DIR/<name>.npy: `recs` (RECORD_DTYPE rows ordered by (game id, ply)) as
+    game_id (float64), ply, move, board [n, 64] (float32) and, for MCTS, `pi` (uint16 [n, MAXM], 0xffff past the
+    move list) as root_visits (float32, -1 padded). Beyond DUMP_BUDGET_BYTES a fixed seeded sample of the rows is
+    written, with the sampled row numbers as rows.npy."""
+    arrays = {"game_id": recs["game_id"].astype(np.float64), "ply": recs["ply"].astype(np.float32),
+              "move": recs["move"].astype(np.float32), "board": recs["board"].astype(np.float32)}
+    if pi is not None:
+        arrays["root_visits"] = np.where(pi == 0xffff, -1, pi.astype(np.int32)).astype(np.float32)
+    n = len(recs)
+    per_row = sum(a.nbytes // max(n, 1) for a in arrays.values()) + 8
+    if n * per_row > DUMP_BUDGET_BYTES:
+        idx = np.sort(np.random.RandomState(0).choice(n, DUMP_BUDGET_BYTES // per_row, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["rows"] = idx.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(a))
 
 
 def _mcts_game_length(sims: int, conv_path: str = None):
@@ -467,12 +514,18 @@ def main():
     G = args.slots
     dev = torch.device("cuda", local)
 
-    def run_chunks(eng, n, chunk, what, t0=None):
+    def run_chunks(eng, n, chunk, what, t0=None, before_last=None):
         # kv_run in chunks so a long region prints progress (stderr, rank 0); each kv_run already
-        # synchronises with the device at its end, so the chunking adds no device idle time
+        # synchronises with the device at its end, so the chunking adds no device idle time.
+        # before_last: called between step n - 1 and step n, which then runs as a kv_run of its own
         done = 0
         while done < n:
             k = min(chunk, n - done)
+            if before_last is not None:
+                if done == n - 1:
+                    before_last()
+                else:
+                    k = min(k, n - 1 - done)
             eng.run(k)
             done += k
             if rank == 0 and (done == n or done % max(chunk, 1) == 0):
@@ -480,7 +533,7 @@ def main():
                 print(f"bench: {what} {done}/{n}{el}", file=sys.stderr, flush=True)
 
     def measure(precision, algo="auto", sims=sims, steps=steps, warmup=warmup, keep=False, tag="main",
-                eval_mode="faithful", weights="init"):
+                eval_mode="faithful", weights="init", mark_last=False):
         eng = SelfPlayEngine(synthetic_state_dict(42, weights), slots=G, n_games=1 << 40, seed=42, max_moves=None,
                              batch=16, sims=sims, game_id_base=rank, game_id_stride=world,
                              eval_mode=(EVAL_LAZY if (eval_mode == "lazy" and sims == 0) else
@@ -496,7 +549,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run_chunks(eng, steps, chunk, f"{tag} timed", t0)
+        # mark_last (--dump-outputs): the record count before the last timed step -- the rows after it are that
+        # step's (one counter read on the host, after the kv_run that has already synchronised)
+        last = {}
+        run_chunks(eng, steps, chunk, f"{tag} timed", t0,
+                   (lambda: last.update(first_row=eng.stats()["records"])) if mark_last else None)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -523,10 +580,12 @@ def main():
         if keep:  # the timed region's experience, left in HBM for the gather (MCTS: with pi)
             out["recs_dev"], out["gms"] = eng.records_device(), eng.games()
             out["pi_dev"] = eng.root_visits_device() if sims > 0 else None
+            out["last_first_row"] = last.get("first_row")
         eng.close()
         return out
 
-    m = measure(args.precision, args.algo, keep=True, eval_mode=args.eval, weights=args.weights)
+    m = measure(args.precision, args.algo, keep=True, eval_mode=args.eval, weights=args.weights,
+                mark_last=bool(args.dump_outputs))
     calib_ranks = None
     if world > 1:  # every rank must run the same conv path (the calibration is per process)
         calib_ranks = [None] * world
@@ -545,13 +604,20 @@ def main():
     if world > 1:
         dist.barrier()
     tg = time.perf_counter()
-    pi_dev = m.pop("pi_dev")
+    pi_dev, recs_dev = m.pop("pi_dev"), m.pop("recs_dev")
     if pi_dev is not None:  # (s, pi, z): records + root visit counts (BASELINE config C4)
-        recs_all, gms_all, pi_all = gather_experience(m.pop("recs_dev"), m["gms"], dst=0, pi=pi_dev)
+        recs_all, gms_all, pi_all = gather_experience(recs_dev, m["gms"], dst=0, pi=pi_dev)
     else:
-        recs_all, gms_all = gather_experience(m.pop("recs_dev"), m["gms"], dst=0)
+        recs_all, gms_all = gather_experience(recs_dev, m["gms"], dst=0)
         pi_all = None
     gather_ms = (time.perf_counter() - tg) * 1e3 if world > 1 else None
+    if args.dump_outputs:
+        # the last timed step's rows of the record buffer (allocation order: the rows after the count read
+        # before that step), gathered and ordered as the whole region's experience is
+        lo = m["last_first_row"]
+        last = gather_experience(recs_dev[lo:], m["gms"][:0], dst=0, pi=pi_dev[lo:] if pi_dev is not None else None)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last[0], last[2] if pi_dev is not None else None)
     n_records = int(len(recs_all)) if recs_all is not None else 0
     # wire bytes: 80-B records + pi as legal-move prefixes (2 B per legal move + a 2-B count per record,
     # distributed.pack_pi); the padded uint16 [n, MAXM] form would be 640 B per record

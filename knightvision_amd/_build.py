@@ -4,6 +4,7 @@ from __future__ import annotations
 import glob
 import os
 import subprocess
+import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libkv.so")
@@ -23,20 +24,23 @@ def stale() -> bool:
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not stale():
         return LIB
-    objs = []
-    procs = []
-    for s in SRC:
-        o = os.path.join("/tmp", "kvbuild_" + os.path.basename(s) + ".o")
-        cmd = [HIPCC, *FLAGS, "-c", s, "-o", o]
-        if verbose:
-            print(" ".join(cmd))
-        procs.append((subprocess.Popen(cmd), cmd))
-        objs.append(o)
-    for p, cmd in procs:
-        if p.wait() != 0:
-            raise RuntimeError("hipcc failed: " + " ".join(cmd))
-    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB + ".tmp", *objs]
-    subprocess.check_call(cmd)
+    # the objects go to a directory of this build's own (another user's or a concurrent build's leftovers
+    # under a fixed name could not be overwritten)
+    with tempfile.TemporaryDirectory(prefix="kvbuild_") as tmp:
+        objs = []
+        procs = []
+        for s in SRC:
+            o = os.path.join(tmp, os.path.basename(s) + ".o")
+            cmd = [HIPCC, *FLAGS, "-c", s, "-o", o]
+            if verbose:
+                print(" ".join(cmd))
+            procs.append((subprocess.Popen(cmd), cmd))
+            objs.append(o)
+        for p, cmd in procs:
+            if p.wait() != 0:
+                raise RuntimeError("hipcc failed: " + " ".join(cmd))
+        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB + ".tmp", *objs]
+        subprocess.check_call(cmd)
     os.replace(LIB + ".tmp", LIB)
     return LIB
 

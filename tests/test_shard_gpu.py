@@ -163,15 +163,15 @@ def test_rccl_gather_path_world1():
 
 
 def test_bench_json_line_contract():
-    """bench.py's one JSON line (the driver's contract) on a tiny MCTS config, run as the driver runs it (a
-    child process): every required key, value = completed backups / timed seconds, roofline + cpu_baseline
+    """bench.py --full's one JSON line (the driver's contract) on a tiny MCTS config, run as the driver runs it
+    (a child process): every required key, value = completed backups / timed seconds, roofline + cpu_baseline
     objects present."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KV_CPU_WORKERS="2")
-    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--slots", "32", "--sims", "8",
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--slots", "32", "--sims", "8",
                           "--steps", "2", "--warmup", "1", "--alt-precision=", "--ref-block", "0",
                           "--cpu-seconds", "2"], capture_output=True, text=True, timeout=240, env=env, cwd=repo)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -195,6 +195,43 @@ def test_bench_json_line_contract():
     assert d["roofline"]["kernel"].startswith(("wino88i32_gemm_r3k64_kernel<512,", "wino88i32_gemm_lagt_kernel<512,"))
     assert d["roofline"]["sclk_mhz"] is None or 500 < d["roofline"]["sclk_mhz"] < 2600
     assert d["trained_weights_path"]["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain bench.py run (no --full) times the headline alone -- no CPU baseline, no side block -- and
+    --dump-outputs writes the last timed step's records and root visit counts, ordered by game id: the rows of
+    the third ply of an engine run in this process on the same configuration (no game ends inside 3 plies)."""
+    import json
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--slots", "32",
+                          "--sims", "8", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "o")],
+                         capture_output=True, text=True, timeout=240, cwd=repo)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "calibration"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["unit"] == "sims/s" and d["dtype"] == "fp32"
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 * 2 - 32 * 8 * 2) < 1e-6 * 32 * 8 * 2
+    for k in ("cpu_baseline", "trained_weights_path", "ref_selection", "fp32_winograd88", "f64w_path",
+              "alt_precision", "fp32_direct"):
+        assert k not in d, k
+    assert d["roofline"]["clock"] is None
+    with SelfPlayEngine(SD, slots=32, n_games=1 << 40, seed=42, max_moves=None, batch=16, sims=8,
+                        record_cap=1 << 16, keep_root_visits=True) as eng:
+        eng.run(3)
+        recs, pi = eng.records(), eng.root_visits()
+    sel = recs["ply"] == 2
+    assert sel.sum() == 32
+    got = {k: np.load(tmp_path / "o" / (k + ".npy")) for k in ("game_id", "ply", "move", "board", "root_visits")}
+    assert got["game_id"].dtype == np.float64 and all(got[k].dtype == np.float32 for k in got if k != "game_id")
+    assert np.array_equal(got["game_id"], recs["game_id"][sel]) and np.array_equal(got["ply"], recs["ply"][sel])
+    assert np.array_equal(got["move"], recs["move"][sel]) and np.array_equal(got["board"], recs["board"][sel])
+    assert np.array_equal(got["root_visits"], pi[sel])
+    assert (np.where(got["root_visits"] < 0, 0, got["root_visits"]).sum(axis=1) == 8).all()
 
 
 def _ddp_world1(port, q):

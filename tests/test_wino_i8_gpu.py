@@ -185,6 +185,102 @@ def _out(M, scale, shift, resid, flags):
     return Y, dg, ex
 
 
+def _out_inputs(rows, resid, seed):
+    """M, scale, shift, residual of the fused fp32 output kernel's tests: board 5 all zero after the ReLU (M = 0,
+    residual 0, shift <= 0), every 7th channel 2^-12 below the others, the two 256-channel halves 2^-5 apart."""
+    rng = np.random.default_rng(seed)
+    M = (rng.standard_normal((100, rows, 512)) * 0.3).astype(np.float32)
+    M[:, 5, :] = 0.0
+    scale = (0.5 + rng.random(512)).astype(np.float32)
+    scale[::7] *= np.float32(2.0 ** -12)  # channels far below the row max
+    scale[256:] *= np.float32(2.0 ** -5)  # the two segments at different scales
+    shift = (rng.standard_normal(512) * 0.1).astype(np.float32)
+    shift = -np.abs(shift)  # M = 0 (and resid = 0) on board 5: ReLU(shift) = 0
+    R = (np.abs(rng.standard_normal((rows, 64, 512))) * 0.5).astype(np.float32) if resid else None
+    if resid:
+        R[5] = 0.0
+    return M, scale, shift, R
+
+
+def _check_out_against_fp64(M, scale, shift, R, Y, dg, ex, r3):
+    """The three checks of test_i8f32_out_kernel_against_fp64_transforms on one result (Y [rows][64][512], digits
+    [100][16][rows][3 or 4][32], exponents [100][rows]) -> the largest ratio of each."""
+    from tests._wino_emul import (input_transform_abs, input_transform_f64, output_transform_abs,
+                                  output_transform_f64)
+    u = 2.0 ** -24
+    rows = M.shape[1]
+    M64, sc, sh = M.astype(np.float64), scale.astype(np.float64), shift.astype(np.float64)
+    res = R.astype(np.float64) if R is not None else 0.0
+    # Y
+    T = output_transform_f64(M64) * sc
+    want = np.maximum(T + sh + res, 0.0)
+    Yk = Y.astype(np.float64)
+    boundY = 24 * u * output_transform_abs(M64) * np.abs(sc) + 2 * u * (np.abs(T) + np.abs(sh) + np.abs(res)) + u * Yk
+    errY = np.abs(Yk - want)
+    rY = float((errY / np.maximum(boundY, 1e-300)).max())
+    assert (errY <= boundY).all(), rY
+    assert not Y[5].any() and (want > 0).mean() > 0.2
+    # exponents: the rule on numpy's row max, moved by the transform's rounding bound either way
+    V64 = input_transform_f64(Yk, optimize=True)
+    VB = 20 * u * input_transform_abs(Yk)
+    m, delta = np.abs(V64).max(-1), VB.max(-1)
+    assert ((m - delta > 0) | (m == 0)).all()  # (of the input: no row's max is within its own rounding of zero)
+    rule = D.row_exponents_r3 if r3 else D.row_exponents
+    lo, hi = rule((m - delta)[..., None]), rule((m + delta)[..., None])
+    assert (lo[m == 0] == 0).all() and (m[:, 5] == 0).all()
+    bad = (ex < lo) | (ex > hi)
+    assert not bad.any(), (int(bad.sum()), ex[bad][:4], lo[bad][:4], hi[bad][:4])
+    assert (ex[:, 5] == 0).all() and not dg[:, :, 5].any()  # all-zero rows: e = 0, zero digits
+    rE = float((hi > lo).mean())
+    # digits, decoded with the layout's own weights
+    nd = 3 if r3 else 4
+    assert dg.shape == (100, 16, rows, nd, 32)
+    dgt = dg.astype(np.float64).transpose(0, 2, 1, 4, 3)  # [100][rows][16][32][digit]
+    assert np.abs(dgt[..., 0]).max() <= 127
+    dec = np.zeros_like(V64)
+    for d in range(nd):
+        dec += dgt[..., d].reshape(100, rows, 512) * (2.0 ** (-7 - 8 * d) if r3 else 2.0 ** (-7 * (d + 1)))
+    dec = np.ldexp(dec, ex[:, :, None])
+    tol = np.ldexp(1.0, ex - (24 if r3 else 29))[:, :, None] + VB
+    errD = np.abs(dec - V64)
+    rD = float((errD / tol).max())
+    assert (errD <= tol).all(), rD
+    return rY, rE, rD, int((ex != rule(m[..., None])).sum())
+
+
+@pytest.mark.parametrize("resid", [False, True])
+@pytest.mark.parametrize("flags", [1, 1 | 16])
+def test_i8f32_out_kernel_against_fp64_transforms(flags, resid):
+    """wino88i32_out_kernel (flags 1: 4 radix-128 digits; 1 | 16: R3's 3 radix-256 digits), 128 boards, against
+    numpy fp64 transforms (tests/_wino_emul: A^T, B^T derived exactly from the points, pinned on the host against
+    the convolution itself) -- the bit-for-bit test beside it compares two GPU pipelines that inline the same
+    w88_at / w88_bt and BN epilogue. u = 2^-24; the same inputs as that test.
+      Y: T = A^T M A in fp64; |Y - ReLU(T scale + shift (+ resid))| <= 24 u (|A^T| |M| |A|) |scale|
+         + 2 u (|T scale| + |shift| + |resid|) + u |Y|. 24 u: per axis one rounding of each fp32 coefficient plus
+         at most 9 fma / multiply roundings in the generated w88_at chains (kv_wino88.h: o[7] has 9 terms), 10 u,
+         over two axes, plus second-order terms. The epilogue (wino88_out_plane_half, contraction off) rounds
+         twice without a residual -- o * sc, + sh -- and three times with one (+ res): the multiply's u |T scale|,
+         the first add's u |T scale + shift| <= u (|T scale| + |shift|), and the last operation's u |Y| (ReLU is
+         1-Lipschitz; where it clamps, the last rounding's operand is within the other terms of zero). Both fit
+         2 u (|T scale| + |shift| + |resid|) + u |Y| to first order, so the constant is not raised.
+      exponents: V64 = B^T Y B in fp64 of the kernel's own Y, m its row max, delta the row's largest transform
+         bound 20 u (|B^T| |Y| |B|) (w88_bt: at most 8 roundings + the coefficient's per axis): the kernel's row
+         max is within delta of m and the rule is monotone, so rule(m - delta) <= e <= rule(m + delta) on every
+         row (row_exponents_r3 / row_exponents); all-zero rows: e = 0, zero digits.
+      digits: 2^(e-7) sum d_i 2^-8i (R3) / 2^e sum d_i 2^-7(i+1) within 2^(e-24) / 2^(e-29) plus the element's
+         transform bound of V64; |d_0| <= 127.
+    These bounds catch a wrong lane mapping, channel, plane orientation, residual or scale (errors of order
+    one); they do not catch a coefficient that is off by 1e-5 -- the generated tables are pinned entry for entry
+    on the host (test_wino_i8_cpu.py) and every bit by the pipeline comparison. Printed: the largest ratio of
+    each check, the share of rows whose exponent interval is wider than one value, and the rows whose e differs
+    from the rule on numpy's own max."""
+    M, scale, shift, R = _out_inputs(128, resid, 128 + resid + (flags & 16))
+    Y, dg, ex = _out(M, scale, shift, R, flags)
+    rY, rE, rD, ne = _check_out_against_fp64(M, scale, shift, R, Y, dg, ex, bool(flags & 16))
+    print(f"flags {flags} resid {resid}: max |dY| / bound = {rY:.3f}, max |ddigits| / bound = {rD:.3f}, exponent "
+          f"interval wider than one value on {100 * rE:.2f} % of rows, {ne} rows off numpy's own max's exponent")
+
+
 @pytest.mark.parametrize("rows,resid,seg", [(128, False, 0), (128, True, 0), (256, True, 0), (128, True, 2),
                                             (256, False, 2), (128, False, 8), (256, True, 8), (128, False, 16),
                                             (256, True, 16), (128, True, 24), (128, False, 32), (384, True, 32),
@@ -196,17 +292,7 @@ def test_i8f32_out_kernel_writes_the_slice_kernels_digits(rows, resid, seg):
     form wino88i32_out2_kernel; seg 32: the persistent LDS-DMA form wino88i32_outp_kernel, 384 rows = 1.5 boards
     per CU, so workgroups loop over different board counts; seg 16: 3 radix-256 digits). Board 5 is all zero
     after the ReLU (its V rows: exponent 0, digits 0); every 7th channel sits 2^-12 below the others."""
-    rng = np.random.default_rng(rows + resid + seg)
-    M = (rng.standard_normal((100, rows, 512)) * 0.3).astype(np.float32)
-    M[:, 5, :] = 0.0
-    scale = (0.5 + rng.random(512)).astype(np.float32)
-    scale[::7] *= np.float32(2.0 ** -12)  # channels far below the row max
-    scale[256:] *= np.float32(2.0 ** -5)  # the two segments at different scales
-    shift = (rng.standard_normal(512) * 0.1).astype(np.float32)
-    shift = -np.abs(shift)  # M = 0 (and resid = 0) on board 5: ReLU(shift) = 0
-    R = (np.abs(rng.standard_normal((rows, 64, 512))) * 0.5).astype(np.float32) if resid else None
-    if resid:
-        R[5] = 0.0
+    M, scale, shift, R = _out_inputs(rows, resid, rows + resid + seg)
     Yf, df, ef = _out(M, scale, shift, R, 1 | seg)
     Ys, ds, es = _out(M, scale, shift, R, seg & 18)  # the slice-kernel form of the same exponents / digits
     assert np.array_equal(Yf.view(np.uint32), Ys.view(np.uint32))
@@ -298,28 +384,70 @@ def _error_bound_r8(V, U, M):
     return b + np.abs(M) * 2.0 ** -51
 
 
-@pytest.mark.parametrize("digits", [4, 5, "r8"])
-def test_i8_gemm_within_derived_bound_of_fp64_product(digits):
-    """M of the int8-digit GEMM against an fp64 matmul of the UNSPLIT operands, on adversarial rows:
-    channels spread over 2^-30 .. 1 of their row's max (so most values keep far fewer than the block's 28 /
-    35 bits), all-equal rows, rows with one large channel, and sign-alternating rows. Every element must be
-    within the bound derived from the arithmetic (_error_bound): per-row block fixed point of 7 x digits
-    bits, digit pairs i + j < digits, exact int32 levels, one rounding."""
-    rng = np.random.default_rng(40 + (6 if digits == "r8" else digits))
-    X, R, K = 100, 128, 512
+def _error_bound_r3(V, U, M):
+    """_error_bound for KV_PATH_WINO88_I8F32R3: a 2^-e = 2^-7 sum_i d_i 2^-8i + rho, |rho| <= 2^-24 (half a
+    unit of N = rint(a 2^(23 - e)), the 24-bit block), the 6 pairs i + j <= 2 of the 3 radix-256 digits kept
+    (exact int32 levels, exact combine), M rounded to fp32 once:
+        |M - V U^T| <= 2^(ev + eu) [rho (sum |a 2^-ev| + sum |b 2^-eu|) + K rho^2
+                                   + sum_{i + j > 2} |d_i| . |e_j| 2^(-14 - 8 (i + j))] + 2^-24 |M|."""
+    K = V.shape[-1]
+    ev, eu = D.row_exponents_r3(V), D.row_exponents_r3(U)
+    dv, du = np.abs(D.split_r3(V, ev).astype(np.float64)), np.abs(D.split_r3(U, eu).astype(np.float64))
+    rho = 2.0 ** -24
+    an = np.abs(np.ldexp(V, (-ev[..., None]).astype(np.int32))).sum(-1)
+    bn = np.abs(np.ldexp(U, (-eu[..., None]).astype(np.int32))).sum(-1)
+    b = rho * (an[:, :, None] + bn[:, None, :]) + K * rho * rho
+    for i in range(3):
+        for j in range(3):
+            if i + j > 2:
+                b = b + np.matmul(dv[i], np.swapaxes(du[j], 1, 2)) * 2.0 ** (-14 - 8 * (i + j))
+    b = np.ldexp(b, (ev[:, :, None] + eu[:, None, :]).astype(np.int32))
+    return b + np.abs(M) * 2.0 ** -24
+
+
+def _adversarial_operands(digits, X=100, R=128, K=512):
+    """The bound test's operands (its docstring); fp32-representable for the fp32-domain forms (4, "r3")."""
+    rng = np.random.default_rng(40 + {"r8": 6, "r3": 7}.get(digits, digits))
     V = np.where(rng.random((X, R, K)) < 0.5, -1.0, 1.0) * np.exp2(-30.0 * rng.random((X, R, K)))
     V *= np.exp2(rng.integers(-12, 12, size=(X, R, 1)))
     V[:, 0] = 0.75                        # all-equal rows
     V[:, 1] = 1e-9
     V[:, 1, 7] = 3.0                      # one large channel, the rest 2^-31 below it
     V[:, 2] = np.where(np.arange(K) % 2 == 0, 1.0, -1.0) * (1 + 2.0 ** -20)
+    if digits == "r3":
+        V[:, 3] = 8.0 * 127 / 128         # the bump edge: e = 4, every N = 127/256 2^23
+        V[:, 4] = np.nextafter(np.float32(8.0 * 127 / 128), np.float32(0.0))  # one fp32 ulp below it: e = 3
+        V[:, 4, 1::2] *= -1.0
+        V[:, 5] = 5.0 * 2.0 ** -23        # the last binade the block holds: N = +-1 beside the max's 5 2^20
+        V[:, 5, 2::3] *= -1.0
+        V[:, 5, 11] = 5.0
     U = rng.standard_normal((X, 512, K)) * np.exp2(-10.0 * rng.random((X, 512, K)))
     U[:, 3] = -0.3                        # an all-equal weight row
-    if digits == 4:
+    if digits in (4, "r3"):
         V, U = V.astype(np.float32).astype(np.float64), U.astype(np.float32).astype(np.float64)
-    M, _, _ = _run(V, U, 4, seg=2) if digits == "r8" else _run(V, U, digits)
+    return V, U
+
+
+@pytest.mark.parametrize("digits", [4, 5, "r8", "r3"])
+def test_i8_gemm_within_derived_bound_of_fp64_product(digits):
+    """M of the int8-digit GEMM against an fp64 matmul of the UNSPLIT operands, on adversarial rows:
+    channels spread over 2^-30 .. 1 of their row's max (so most values keep far fewer than the block's 28 /
+    35 bits), all-equal rows, rows with one large channel, and sign-alternating rows. Every element must be
+    within the bound derived from the arithmetic (_error_bound): per-row block fixed point of 7 x digits
+    bits, digit pairs i + j < digits, exact int32 levels, one rounding. "r3" (KV_PATH_WINO88_I8F32R3, 24-bit
+    blocks with no spare bit, _error_bound_r3) adds the rows at its rule's edges: all channels at 127/128 2^3
+    (the bump), all one fp32 ulp below that, and one channel at the row max with the rest 2^-23 below it, the
+    last binade the block represents. (On the host, tests/_i8_digits.gemm_r3 as the kernel stays within the
+    bound, and the same arithmetic without the (1, 1) pair leaves most elements outside it.)"""
+    V, U = _adversarial_operands(digits)
+    if digits == "r3":
+        M, _, ex = _run(V, U, 4, seg=3)
+        assert (ex[:, 3] == 4).all() and (ex[:, 4] == 3).all() and (ex[:, 5] == 3).all()
+    else:
+        M, _, _ = _run(V, U, 4, seg=2) if digits == "r8" else _run(V, U, digits)
     M64 = np.matmul(V, np.swapaxes(U, 1, 2))
-    bound = _error_bound_r8(V, U, M) if digits == "r8" else _error_bound(V, U, digits, M)
+    bound = (_error_bound_r8(V, U, M) if digits == "r8" else _error_bound_r3(V, U, M) if digits == "r3"
+             else _error_bound(V, U, digits, M))
     err = np.abs(M - M64)
     ratio = err / np.maximum(bound, 1e-300)
     print(f"digits {digits}: max |M - VU^T| / bound = {ratio.max():.3f}, max |err| / |M| (|M| > 0) = "

@@ -288,6 +288,37 @@ int kv_root_visits_device(kv_engine* e, uint16_t* out_dev, size_t cap, size_t* n
 int kv_sync(kv_engine* e);
 void kv_destroy(kv_engine* e);
 
+/* ------------------------------------------------------ position search ---
+ * PUCT search of n given positions (DESIGN.md "MCTS semantics": the self-play
+ * search from any root, with `leaves` descents in flight per tree and sim-step
+ * under virtual loss, so one position fills a network batch of `leaves` rows;
+ * leaves = 1 is the self-play search bit for bit). No reference counterpart.
+ *
+ * The engine comes from kv_create with slots >= n and sims >= p->sims >= 1 (the
+ * tree pools); c_puct, eval_mode, precision, algo and tree_edge_cap are its
+ * config's, n_games may be 0. An engine serves either kv_run or kv_search:
+ * calling one after the other has been used is KV_EINVAL. states: n 80-byte
+ * state vectors (64 board codes, wtm, king squares, moved flags, ep, as
+ * kv_dev_valid_moves reads them). Position i's numpy stream (the root's
+ * Dirichlet draw) is seeded p->seed + i; with eps = 0 the result does not
+ * depend on it. A shrunk tree_edge_cap that overflows raises KV_EOVERFLOW. */
+#define KV_MAX_LEAVES 64
+typedef struct { int sims; int leaves; double eps, alpha; uint64_t seed; } kv_search_params;
+typedef struct {
+    int32_t status;   /* 0 searched, 1 checkmated root, 2 stalemate, 3 draw (kings only) */
+    int32_t n_moves, sims, best, pv_len, steps, nn_rows, pad; /* best: first maximum of visits (-1: not
+                         searched); steps: sim-steps run; nn_rows: the root's row + the leaves evaluated */
+    float root_value; /* network value of the root, white perspective; terminal: that value */
+    float best_q;
+    uint16_t pv[16];  /* first-max-visit edges from the root through expanded children, as move words */
+    uint16_t moves[KV_MAXM];  /* from | to<<6 | flags<<12, root list order (kv_dev_valid_moves' words) */
+    int32_t  visits[KV_MAXM]; /* -1 past n_moves */
+    float    q[KV_MAXM], prior[KV_MAXM]; /* q = W/N from the root mover's side, 0 where unvisited */
+} kv_search_result;
+int kv_search(kv_engine* e, const int8_t* states /*[n][80]*/, int n,
+              const kv_search_params* p, kv_search_result* out /*[n]*/);
+size_t kv_sizeof_search_result(void);
+
 /* ------------------------------------------------- device test entry points ---
  * Run one device kernel over host-provided inputs (copies in and out). They
  * exist so parity tests can call the product kernels through the C ABI. */

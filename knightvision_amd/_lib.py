@@ -71,7 +71,24 @@ class PgnRecord(C.Structure):
 PGN_OUTCOME_NONE = -128
 MAXM = 320  # KV_MAXM, move-list capacity per position
 
+MAX_LEAVES = 64  # KV_MAX_LEAVES
+
+
+class SearchParams(C.Structure):
+    _fields_ = [("sims", C.c_int), ("leaves", C.c_int), ("eps", C.c_double), ("alpha", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+class SearchResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_moves", C.c_int32), ("sims", C.c_int32), ("best", C.c_int32),
+                ("pv_len", C.c_int32), ("steps", C.c_int32), ("nn_rows", C.c_int32), ("pad", C.c_int32),
+                ("root_value", C.c_float), ("best_q", C.c_float), ("pv", C.c_uint16 * 16),
+                ("moves", C.c_uint16 * MAXM), ("visits", C.c_int32 * MAXM), ("q", C.c_float * MAXM),
+                ("prior", C.c_float * MAXM)]
+
+
 assert C.sizeof(Record) == 80 and C.sizeof(Game) == 32 and C.sizeof(PgnRecord) == 120
+assert C.sizeof(SearchParams) == 32 and C.sizeof(SearchResult) == 72 + 14 * MAXM
 
 
 def _declare(L):
@@ -106,6 +123,8 @@ def _declare(L):
         "kv_sync": ([vp], i),
         "kv_reset_records": ([vp], i),
         "kv_destroy": ([vp], None),
+        "kv_search": ([vp, P(C.c_int8), i, P(SearchParams), P(SearchResult)], i),
+        "kv_sizeof_search_result": ([], sz),
         "kv_dev_valid_moves": ([i, P(C.c_int8), i, P(C.c_uint16), i, P(i), P(C.c_int8), P(C.c_uint8)], i),
         "kv_dev_make_move": ([i, P(C.c_int8), P(i), i], i),
         "kv_dev_attacks": ([i, P(C.c_int8), i, P(C.c_uint64)], i),
@@ -155,6 +174,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_net_calibration", "kv_engine_calibration",
             "kv_create",
             "kv_load_weights", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_root_visits", "kv_root_visits_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
+            "kv_search", "kv_sizeof_search_result",
             "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm",
             "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_i8gemm_bench",
             "kv_dev_gemm_clock", "kv_dev_out_phases",
@@ -173,7 +193,10 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise KVError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(the HIP library is required; there is no CPU fallback)")
-        _lib = _declare(C.CDLL(LIB_PATH))
+        L = _declare(C.CDLL(LIB_PATH))
+        if hasattr(L, "kv_sizeof_search_result"):  # EXPORTED (checked by build()) lists what must be there
+            assert L.kv_sizeof_search_result() == C.sizeof(SearchResult), "kv_search_result: ctypes mirror differs"
+        _lib = L
     return _lib
 
 

@@ -1,5 +1,6 @@
 // Shared device state of the self-play engine (kv_engine.hip: reference
-// move selection; kv_mcts.hip: PUCT search).
+// move selection; kv_mcts.hip: PUCT search; kv_search.hip: the search of
+// given positions, kv_search).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -131,6 +132,43 @@ struct Tree {  // per-slot SoA edge pools + node records, slot i at i*ecap / i*n
     int ecap, ncap;
     float c_puct;
     int sims;
+    uint16_t* e_V;  // position search with several leaves in flight (kv_search.hip): descents in flight per edge
+};
+
+// ---- position search (kv_search.hip): per-tree state, per-(tree, j) descents of the running sim-step ----
+enum : int { SR_SEARCHED = 0, SR_CHECKMATED = 1, SR_STALEMATE = 2, SR_DRAW = 3 };
+
+struct SearchSlot {
+    int status;     // SR_*
+    int done;       // backups completed
+    int vroot;      // descents in flight (nonzero only inside a sim-step)
+    int accepted;   // descents of the running sim-step
+    int steps;      // sim-steps run
+    int leaf_rows;  // leaves sent to the network
+    float term_value;  // SR_CHECKMATED / SR_STALEMATE / SR_DRAW: the root's value, white perspective
+    int pad;
+};
+
+struct SearchLeaf {
+    int path_len;
+    int leaf_edge;
+    int pending;  // 1: row tree * L + j of the step's network batch is this leaf
+    int n;        // its legal moves
+    float value;  // terminal value (white perspective) when !pending
+    int pad[3];
+};
+
+struct SearchWs {  // workspaces of kv_search, rows = positions x leaves; reserved at the first search, only grown
+    SearchSlot* ss;       // [slots]
+    SearchLeaf* lf;       // [rows]
+    int* paths;           // [rows][ncap]
+    int8_t* lboards;      // [rows][64]
+    uint16_t* lmoves;     // [rows][MAXM]
+    int* lcnt;            // [rows]
+    float* llogits;       // [rows][MAXM]
+    float* lvalues;       // [rows]
+    int* remaining;       // trees with done < sims after the last backup
+    kv_search_result* res;  // [slots]
 };
 
 __device__ inline float wave_max(float v) {
@@ -142,6 +180,26 @@ __device__ inline float wave_sum(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
     return v;
+}
+
+// the wave's maximum and, among equal maxima, the smallest index (kv_mcts.hip, kv_search.hip)
+__device__ inline void wave_argmax_first(float& best, int& idx) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ob = __shfl_xor(best, m);
+        const int oi = __shfl_xor(idx, m);
+        if (ob > best || (ob == best && oi < idx)) {
+            best = ob;
+            idx = oi;
+        }
+    }
+}
+
+// PUCT score; identical op order in kvo_mcts (oracle), no contraction
+__device__ inline float puct(float c_puct, float P, float sq, int N, float W) {
+    const float u = c_puct * P * sq / (float)(1 + N);
+    const float q = N > 0 ? W / (float)N : 0.0f;
+    return q + u;
 }
 
 // torch.softmax over 4096 fp32 logits (self_play.py:150): max, exp(x-max),
@@ -336,5 +394,15 @@ int mcts_choose(const DevCfg& cfg, const Tree& t, Slot* slots, int8_t* boards, u
                 int8_t* last_board, Ctr* ctr, hipStream_t st);
 int hash_eval(const int8_t* boards, int rows, float* logits, float* values, hipStream_t st);
 int hash_legal(const Tree& t, int rows, hipStream_t st);
+
+// position search launches (kv_search.hip), all on `st`; n trees, L leaves in flight per tree
+int search_load(const Tree& t, const SearchWs& w, Slot* slots, int8_t* boards, uint16_t* moves, int8_t* root_rows,
+                uint32_t* np_mt, const int8_t* states, unsigned long long seed, int n, int L, Ctr* ctr,
+                hipStream_t st);
+int search_select(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr, int sims,
+                  int n, int L, hipStream_t st);
+int search_backup_select(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr,
+                         int sims, int n, int L, hipStream_t st);
+int search_result(const Tree& t, const SearchWs& w, const Slot* slots, Ctr* ctr, int sims, int n, hipStream_t st);
 
 }  // namespace kv

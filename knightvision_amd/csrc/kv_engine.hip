@@ -475,6 +475,17 @@ struct kv_engine {
     // (kv_destroy) waits for that copy on e->st
     hipEvent_t copy_done = nullptr;
     bool copy_pending = false;
+    // kv_search: an engine serves either kv_run or kv_search (used: 0 neither yet, 1 kv_run, 2 kv_search)
+    int used = 0;
+    kv::SearchWs sw = {};
+    size_t sw_rows = 0;           // rows (positions x leaves) the leaf workspaces hold
+    int8_t* s_states = nullptr;   // [slots][80]
+    int8_t* s_rboards = nullptr;  // root batch [max(slots, 17)][64], [4096] logits and a value per row
+    float* s_rlogits = nullptr;
+    float* s_rvalues = nullptr;
+    float* s_hlogits = nullptr;   // KV_EVAL_HASH: the full rows k_hash_eval writes for the leaf batch
+    size_t s_hrows = 0;
+    int* s_rem_host = nullptr;    // pinned: trees with done < sims, read back once per sim-step
 };
 
 // order e->st after an outstanding device-to-device copy of the engine's buffers on a caller stream
@@ -742,6 +753,9 @@ static int eng_eval(kv_engine* e, const int8_t* boards, int rows, bool leaf = fa
 
 int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
     KV_REQUIRE(e && e->loaded, KV_EINVAL, "kv_run: engine has no weights");
+    KV_REQUIRE(e->used != 2, KV_EINVAL,
+               "kv_run: this engine has searched positions (kv_search); an engine serves either kv_run or kv_search");
+    e->used = 1;
     KV_HIP(hipSetDevice(e->cfg.device));
     const auto t0 = std::chrono::steady_clock::now();
     const int S = e->cfg.slots;
@@ -841,6 +855,163 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
     e->wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return KV_OK;
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------ position search --
+// (re)allocate a search buffer; the stream is idle when this runs
+template <class T>
+static int search_alloc(T*& p, size_t count, bool zero = false) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    const hipError_t er = hipMalloc(&p, count * sizeof(T));
+    if (er != hipSuccess) {
+        p = nullptr;
+        kv::set_error("kv_search: hipMalloc (%zu B): %s", count * sizeof(T), hipGetErrorString(er));
+        return KV_ENOMEM;
+    }
+    if (zero) KV_HIP(hipMemset(p, 0, count * sizeof(T)));
+    return KV_OK;
+}
+
+// the workspaces of a search over n positions with L leaves in flight: reserved at the first search that asks
+// for them, only grown
+static int search_reserve(kv_engine* e, int n, int L) {
+    const size_t S = (size_t)e->cfg.slots, RR = std::max<size_t>(S, 17), rows = (size_t)n * L;
+    const bool hash = e->dc.eval_mode == KV_EVAL_HASH;
+    kv::SearchWs& w = e->sw;
+    kv::Tree& t = e->tree;
+    int rc = KV_OK;
+    const bool grow = rows > e->sw_rows, grow_h = hash && rows > e->s_hrows;
+    if (w.ss && !grow && !grow_h && (L == 1 || t.e_V)) return KV_OK;
+    KV_HIP(hipStreamSynchronize(e->st));
+    if (!w.ss) {
+        if ((rc = search_alloc(w.ss, S)) || (rc = search_alloc(w.remaining, 1)) || (rc = search_alloc(w.res, S)) ||
+            (rc = search_alloc(e->s_states, S * 80)) || (rc = search_alloc(e->s_rboards, RR * 64, true)) ||
+            (rc = search_alloc(e->s_rlogits, RR * 4096)) || (rc = search_alloc(e->s_rvalues, RR)))
+            return rc;
+        if (hipHostMalloc(&e->s_rem_host, sizeof(int)) != hipSuccess) {
+            e->s_rem_host = nullptr;
+            kv::set_error("kv_search: hipHostMalloc failed");
+            return KV_ENOMEM;
+        }
+    }
+    if (grow) {
+        e->sw_rows = 0;
+        // lboards zeroed: a row no leaf was written to yet is still a board the network can read
+        if ((rc = search_alloc(w.lf, rows)) || (rc = search_alloc(w.paths, rows * (size_t)t.ncap)) ||
+            (rc = search_alloc(w.lboards, rows * 64, true)) || (rc = search_alloc(w.lmoves, rows * kv::MAXM)) ||
+            (rc = search_alloc(w.lcnt, rows, true)) || (rc = search_alloc(w.llogits, rows * kv::MAXM)) ||
+            (rc = search_alloc(w.lvalues, rows)))
+            return rc;
+        e->sw_rows = rows;
+    }
+    if (grow_h) {
+        e->s_hrows = 0;
+        if ((rc = search_alloc(e->s_hlogits, rows * 4096))) return rc;
+        e->s_hrows = rows;
+    }
+    if (L > 1 && !t.e_V && (rc = search_alloc(t.e_V, S * (size_t)t.ecap, true))) return rc;
+    return KV_OK;
+}
+
+// one network pass of a search (or the hash test evaluator): the root rows, or the step's leaf batch with
+// only the leaves' legal logits (kv_net_forward_boards_legal)
+static int search_eval(kv_engine* e, const int8_t* boards, int rows, bool leaf) {
+    const kv::SearchWs& w = e->sw;
+    if (e->dc.eval_mode == KV_EVAL_HASH) {
+        int rc = kv::hash_eval(boards, rows, leaf ? e->s_hlogits : e->s_rlogits, leaf ? w.lvalues : e->s_rvalues,
+                               e->st);
+        if (rc || !leaf) return rc;
+        kv::Tree lt = e->tree;  // k_hash_legal reads the batch's counts and writes its logits through the tree
+        lt.leaf_cnt = w.lcnt;
+        lt.leaf_logits = w.llogits;
+        return kv::hash_legal(lt, rows, e->st);
+    }
+    return leaf ? kv::net_forward_boards_legal_internal(e->net, boards, rows, w.lmoves, w.lcnt, kv::MAXM, w.llogits,
+                                                        w.lvalues, e->st)
+                : kv::net_forward_boards_internal(e->net, boards, rows, e->s_rlogits, e->s_rvalues, e->st);
+}
+
+extern "C" {
+
+int kv_search(kv_engine* e, const int8_t* states, int n, const kv_search_params* p, kv_search_result* out) {
+    KV_REQUIRE(e && states && p && out, KV_EINVAL, "kv_search: NULL argument");
+    KV_REQUIRE(n > 0 && n <= e->cfg.slots, KV_EINVAL, "kv_search: %d positions, the engine holds 1..%d (slots)", n,
+               e->cfg.slots);
+    KV_REQUIRE(p->leaves >= 1 && p->leaves <= KV_MAX_LEAVES, KV_EINVAL, "kv_search: leaves %d out of range [1, %d]",
+               p->leaves, KV_MAX_LEAVES);
+    KV_REQUIRE(e->cfg.sims >= 1, KV_EINVAL, "kv_search: the engine was created without tree pools (sims 0)");
+    KV_REQUIRE(p->sims >= 1 && p->sims <= e->cfg.sims, KV_EINVAL,
+               "kv_search: sims %d out of range [1, %d] (the engine's sims size its tree pools)", p->sims,
+               e->cfg.sims);
+    KV_REQUIRE(p->alpha >= 2.2250738585072014e-308 && p->alpha < 1.0, KV_EINVAL,
+               "kv_search: alpha must be a normal double in (0,1), got %g", p->alpha);
+    KV_REQUIRE(p->eps >= 0.0 && p->eps <= 1.0, KV_EINVAL, "kv_search: eps %g out of range [0, 1]", p->eps);
+    KV_REQUIRE(e->used != 1, KV_EINVAL,
+               "kv_search: this engine has run self-play (kv_run); an engine serves either kv_run or kv_search");
+    KV_REQUIRE(e->loaded, KV_EINVAL, "kv_search: engine has no weights");
+    for (int i = 0; i < n; ++i) {
+        const int8_t* v = states + (size_t)i * 80;
+        bool ok = (v[64] == 0 || v[64] == 1) && v[75] >= -1 && v[75] < 8 && v[76] >= -1 && v[76] < 8 &&
+                  (v[75] < 0) == (v[76] < 0);
+        for (int q = 0; q < 64; ++q) ok = ok && v[q] >= 0 && v[q] <= 12;
+        for (int q = 65; q < 69; ++q) ok = ok && v[q] >= 0 && v[q] < 8;
+        KV_REQUIRE(ok, KV_EINVAL, "kv_search: position %d is not a state vector (codes 0..12, wtm 0/1, king "
+                   "squares 0..7, ep -1..7)", i);
+    }
+    e->used = 2;
+    KV_HIP(hipSetDevice(e->cfg.device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const int L = p->leaves, rows = n * L;
+    int rc = search_reserve(e, n, L);
+    if (rc) return rc;
+    const kv::SearchWs& w = e->sw;
+    const kv::Tree& t = e->tree;
+    hipStream_t st = e->st;
+    // a search that overflowed a shrunk pool leaves the engine usable: the flag is this search's own
+    KV_HIP(hipMemsetAsync(&e->ctr->error, 0, sizeof(int), st));
+    KV_HIP(hipMemcpyAsync(e->s_states, states, (size_t)n * 80, hipMemcpyHostToDevice, st));
+    if ((rc = kv::search_load(t, w, e->slots, e->boards, e->moves, e->s_rboards, e->np_mt, e->s_states, p->seed, n,
+                              L, e->ctr, st)))
+        return rc;
+    // the network class (<= 16 boards or above) is that of positions x leaves for the whole search: the
+    // root batch of a larger class is padded to 17 rows (empty boards past n)
+    const int root_rows = rows > 16 ? std::max(n, 17) : n;
+    if ((rc = search_eval(e, e->s_rboards, root_rows, false))) return rc;
+    kv::DevCfg dc = e->dc;
+    dc.slots = n;
+    dc.eps = p->eps;
+    dc.alpha = p->alpha;
+    if ((rc = kv::mcts_root(dc, t, e->slots, e->moves, e->s_rlogits, e->s_rvalues, e->probs, e->np_mt, e->ctr, st)))
+        return rc;
+    if ((rc = kv::search_select(t, w, e->slots, e->boards, e->ctr, p->sims, n, L, st))) return rc;
+    // every step accepts at least one descent per unfinished tree: at most sims steps. With one leaf in
+    // flight it accepts exactly one, so the step count is known and the host reads nothing back (kv_run's
+    // loop); with more, collisions decide it: one counter per step, trees with done < sims
+    const bool counted = L > 1;
+    for (int step = 0;; ++step) {
+        KV_REQUIRE(step < p->sims, KV_EHIP, "kv_search: %d sim-steps without finishing %d sims", step, p->sims);
+        if ((rc = search_eval(e, w.lboards, rows, true))) return rc;
+        if (counted) KV_HIP(hipMemsetAsync(w.remaining, 0, sizeof(int), st));
+        if ((rc = kv::search_backup_select(t, w, e->slots, e->boards, e->ctr, p->sims, n, L, st))) return rc;
+        if (!counted) {
+            if (step + 1 == p->sims) break;
+            continue;
+        }
+        KV_HIP(hipMemcpyAsync(e->s_rem_host, w.remaining, sizeof(int), hipMemcpyDeviceToHost, st));
+        KV_HIP(hipStreamSynchronize(st));
+        if (*e->s_rem_host == 0) break;
+    }
+    if ((rc = kv::search_result(t, w, e->slots, e->ctr, p->sims, n, st))) return rc;
+    KV_HIP(hipMemcpyAsync(out, w.res, (size_t)n * sizeof(kv_search_result), hipMemcpyDeviceToHost, st));
+    KV_HIP(hipStreamSynchronize(st));
+    e->steps += 1;
+    e->wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return eng_counters(e);
+}
+
+size_t kv_sizeof_search_result(void) { return sizeof(kv_search_result); }
 
 int kv_reset_records(kv_engine* e) {
     KV_REQUIRE(e, KV_EINVAL, "kv_reset_records: NULL");
@@ -974,10 +1145,14 @@ void kv_destroy(kv_engine* e) {
                     t.e_move, t.e_P, t.e_N, t.e_W, t.e_child, t.node, t.path,
                     t.leaf_moves, e->ms, e->nn_boards, e->probs, e->sqrt_tab, t.root_visits, t.leaf_cnt,
                     t.leaf_logits, e->mc_slot_of, e->mc_row_of, e->mc_boards, e->mc_moves, e->mc_cnt,
-                    e->mc_logits, e->mc_values};
+                    e->mc_logits, e->mc_values,
+                    t.e_V, e->sw.ss, e->sw.lf, e->sw.paths, e->sw.lboards, e->sw.lmoves, e->sw.lcnt, e->sw.llogits,
+                    e->sw.lvalues, e->sw.remaining, e->sw.res, e->s_states, e->s_rboards, e->s_rlogits,
+                    e->s_rvalues, e->s_hlogits};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (e->ctr_host) (void)hipHostFree(e->ctr_host);
+    if (e->s_rem_host) (void)hipHostFree(e->s_rem_host);
     for (auto x : e->ev) (void)hipEventDestroy(x);
     if (e->copy_done) (void)hipEventDestroy(e->copy_done);
     if (e->net) kv_net_destroy(e->net);

@@ -37,25 +37,6 @@
 
 namespace kv {
 
-__device__ inline void wave_argmax_first(float& best, int& idx) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ob = __shfl_xor(best, m);
-        const int oi = __shfl_xor(idx, m);
-        if (ob > best || (ob == best && oi < idx)) {
-            best = ob;
-            idx = oi;
-        }
-    }
-}
-
-// PUCT score; identical op order in kvo_mcts (oracle), no contraction
-__device__ inline float puct(float c_puct, float P, float sq, int N, float W) {
-    const float u = c_puct * P * sq / (float)(1 + N);
-    const float q = N > 0 ? W / (float)N : 0.0f;
-    return q + u;
-}
-
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_mcts_root(DevCfg cfg, Tree t, Slot* slots, const uint16_t* moves,
                                                    const float* logits, const float* values, float* probs,
                                                    uint32_t* np_mt, Ctr* ctr) {

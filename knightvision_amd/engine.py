@@ -166,6 +166,76 @@ class SelfPlayEngine:
             pass
 
 
+SEARCH_DTYPE = np.dtype([("status", "<i4"), ("n_moves", "<i4"), ("sims", "<i4"), ("best", "<i4"), ("pv_len", "<i4"),
+                         ("steps", "<i4"), ("nn_rows", "<i4"), ("pad", "<i4"), ("root_value", "<f4"),
+                         ("best_q", "<f4"), ("pv", "<u2", (16,)), ("moves", "<u2", (_lib.MAXM,)),
+                         ("visits", "<i4", (_lib.MAXM,)), ("q", "<f4", (_lib.MAXM,)),
+                         ("prior", "<f4", (_lib.MAXM,))])
+assert SEARCH_DTYPE.itemsize == C.sizeof(_lib.SearchResult)
+
+SEARCH_STATUS = {0: "searched", 1: "checkmated", 2: "stalemate", 3: "draw"}
+
+
+class PositionSearch:
+    """PUCT search of given positions on one GPU (kv_search, include/kv.h): up to max_positions roots per
+    call, up to max_sims simulations each. The weights are loaded (and the conv path calibrated) once."""
+
+    def __init__(self, weights, *, max_positions, max_sims, c_puct=1.5, eval_mode=EVAL_FAITHFUL, precision="fp32",
+                 algo="auto", tree_edge_cap=0, device=0):
+        L = _lib.lib()
+        cfg = _lib.Config(device=device, slots=int(max_positions), n_games=0, game_id_base=0, game_id_stride=1,
+                          seed=0, seed_mode=SEED_PER_GAME, max_moves=0, batch=1, eps=0.0, alpha=0.3,
+                          sims=int(max_sims), c_puct=c_puct, eval_mode=eval_mode, record_cap=1, recycle=0,
+                          precision=PRECISIONS[precision], algo=ALGOS[algo], tree_edge_cap=int(tree_edge_cap),
+                          keep_root_visits=0)
+        h = C.c_void_p()
+        _lib.check(L.kv_create(C.byref(cfg), C.byref(h)), "kv_create")
+        self.h = h
+        self.cfg = cfg
+        packed = packed_from(weights)
+        _lib.check(L.kv_load_weights(self.h, packed.ctypes.data_as(C.POINTER(C.c_float)), packed.size),
+                   "kv_load_weights")
+
+    def search(self, states, sims, leaves=1, eps=0.0, alpha=0.3, seed=0) -> np.ndarray:
+        """states: [n, 80] int8 state vectors (GameState._state(), the oracle's) -> SEARCH_DTYPE[n]: root visit
+        counts, q, priors and move words in root list order, best move index, principal variation."""
+        st = np.ascontiguousarray(states, dtype=np.int8).reshape(-1, 80)
+        out = np.zeros(len(st), dtype=SEARCH_DTYPE)
+        p = _lib.SearchParams(sims=int(sims), leaves=int(leaves), eps=float(eps), alpha=float(alpha), seed=int(seed))
+        _lib.check(_lib.lib().kv_search(self.h, st.ctypes.data_as(C.POINTER(C.c_int8)), len(st), C.byref(p),
+                                        out.ctypes.data_as(C.POINTER(_lib.SearchResult))), "kv_search")
+        return out
+
+    def calibration(self) -> dict:
+        c = _lib.Calib()
+        _lib.check(_lib.lib().kv_engine_calibration(self.h, C.byref(c)), "kv_engine_calibration")
+        return _lib.calib_dict(c)
+
+    def stats(self) -> dict:
+        st = _lib.Stats()
+        _lib.check(_lib.lib().kv_stats_get(self.h, C.byref(st)), "kv_stats_get")
+        out = {k: getattr(st, k) for k, _ in _lib.Stats._fields_}
+        out["dom_kernel"] = out["dom_kernel"].decode()
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            _lib.lib().kv_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def records_by_game(recs: np.ndarray, games: np.ndarray):
     """-> {game_id: (moves uint16[plies], boards int8[plies,64], reward)}."""
     out = {}

@@ -28,6 +28,17 @@ def get_ai_move(gs, model):
     return valid[norm.index(max(norm))]
 
 
+def search_move(gs, searcher, sims=800, leaves=32):
+    """The PUCT search's move for the position (engine.PositionSearch): the entry of gs.getValidMoves() at the
+    root list index with the most visits (the first of equal maxima); None at a root that is not searched
+    (no legal move, or kings only)."""
+    valid = gs.getValidMoves()
+    row = searcher.search(gs._state()[None], sims, leaves=leaves)[0]
+    if row["status"] != 0:
+        return None
+    return valid[int(row["best"])]
+
+
 def masked_argmax_move(logits: torch.Tensor, legal_indices) -> int:
     """stockfish_play.py:64-84: argmax of the logits restricted to the legal
     move indices (encode_move), -1 when there are none."""

@@ -319,6 +319,30 @@ int kv_search(kv_engine* e, const int8_t* states /*[n][80]*/, int n,
               const kv_search_params* p, kv_search_result* out /*[n]*/);
 size_t kv_sizeof_search_result(void);
 
+/* Search sessions (DESIGN.md "Search sessions"): the trees of the last kv_search follow a game, so that the
+ * subtree under a played move is searched on instead of rebuilt. A kv_search starts a new session; n must be
+ * the session's; both calls are KV_EINVAL before any kv_search. A call that fails on the device (KV_EHIP,
+ * KV_EOVERFLOW) ends the session.
+ *
+ * kv_search_advance plays root move edge[i] (root list index; -1: tree i stays as it is) in every tree: the
+ * child's subtree becomes the tree, its visits, values, priors and move words carried bit for bit; an edge
+ * without an expanded child (never visited, or a move into mate, stalemate or kings only) drops the tree. An
+ * edge >= the root's n_moves, or >= 0 at a root that was not searched, is KV_EINVAL and changes no tree.
+ * states_out (or NULL): the state vectors after the moves (the current ones where edge is -1).
+ *
+ * kv_search_continue searches the current roots up to p->sims root visits, the carried ones counting:
+ * a tree that already holds them runs no step. A dropped tree is searched as kv_search searches a given
+ * position. p->eps must be 0 (no noise at a carried root). out as kv_search, with sims = the root's visits
+ * (carried + new), steps and nn_rows of this call only (no root row for a carried tree); kept (or NULL):
+ * the visits each root held when the call began, 0 for a dropped tree. leaves may differ from call to call.
+ *
+ * kv_search_tree_size: the nodes of tree i and the edges of its pool it occupies (every node's block counted
+ * to its 16-edge boundary); 0, 0 for a root that is not searched or a dropped tree not yet continued. */
+int kv_search_advance(kv_engine* e, int n, const int32_t* edge /*[n]*/, int8_t* states_out /*[n][80] or NULL*/);
+int kv_search_continue(kv_engine* e, int n, const kv_search_params* p, kv_search_result* out /*[n]*/,
+                       int32_t* kept /*[n] or NULL*/);
+int kv_search_tree_size(kv_engine* e, int i, int32_t* nodes, int32_t* edges);
+
 /* ------------------------------------------------- device test entry points ---
  * Run one device kernel over host-provided inputs (copies in and out). They
  * exist so parity tests can call the product kernels through the C ABI. */

@@ -125,6 +125,9 @@ def _declare(L):
         "kv_destroy": ([vp], None),
         "kv_search": ([vp, P(C.c_int8), i, P(SearchParams), P(SearchResult)], i),
         "kv_sizeof_search_result": ([], sz),
+        "kv_search_advance": ([vp, i, P(C.c_int32), P(C.c_int8)], i),
+        "kv_search_continue": ([vp, i, P(SearchParams), P(SearchResult), P(C.c_int32)], i),
+        "kv_search_tree_size": ([vp, i, P(C.c_int32), P(C.c_int32)], i),
         "kv_dev_valid_moves": ([i, P(C.c_int8), i, P(C.c_uint16), i, P(i), P(C.c_int8), P(C.c_uint8)], i),
         "kv_dev_make_move": ([i, P(C.c_int8), P(i), i], i),
         "kv_dev_attacks": ([i, P(C.c_int8), i, P(C.c_uint64)], i),
@@ -174,7 +177,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_net_calibration", "kv_engine_calibration",
             "kv_create",
             "kv_load_weights", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_root_visits", "kv_root_visits_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
-            "kv_search", "kv_sizeof_search_result",
+            "kv_search", "kv_sizeof_search_result", "kv_search_advance", "kv_search_continue", "kv_search_tree_size",
             "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm",
             "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_i8gemm_bench",
             "kv_dev_gemm_clock", "kv_dev_out_phases",

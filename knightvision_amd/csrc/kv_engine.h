@@ -112,7 +112,8 @@ struct MctsSlot {  // per-slot search scratch (kv_mcts.hip)
 constexpr uint16_t NO_CHILD = 0xffff;  // e_child of an unexpanded edge
 
 struct __attribute__((aligned(16))) NodeRec {
-    int first, cnt, N, pad;
+    int first, cnt, N;
+    int value;  // kv_search.hip: bits of the network value the node got at its expansion (a session's re-root)
 };
 
 struct Tree {  // per-slot SoA edge pools + node records, slot i at i*ecap / i*ncap
@@ -158,6 +159,15 @@ struct SearchLeaf {
     int pad[3];
 };
 
+struct SessionSlot {  // per-tree state of a search session (kv_search_advance / kv_search_continue)
+    int status;    // SR_* of the current root
+    int n_moves;   // its move count
+    int kept;      // visits the root held when the last advance / continue began counting (0: dropped or fresh)
+    int fresh;     // 1: the tree was dropped, the next continue builds the root from its network row
+    int root_row;  // 1: the running continue took a root row for this tree
+    int pad[3];
+};
+
 struct SearchWs {  // workspaces of kv_search, rows = positions x leaves; reserved at the first search, only grown
     SearchSlot* ss;       // [slots]
     SearchLeaf* lf;       // [rows]
@@ -169,6 +179,7 @@ struct SearchWs {  // workspaces of kv_search, rows = positions x leaves; reserv
     float* lvalues;       // [rows]
     int* remaining;       // trees with done < sims after the last backup
     kv_search_result* res;  // [slots]
+    SessionSlot* sess;    // [slots]
 };
 
 __device__ inline float wave_max(float v) {
@@ -403,6 +414,13 @@ int search_select(const Tree& t, const SearchWs& w, const Slot* slots, const int
                   int n, int L, hipStream_t st);
 int search_backup_select(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr,
                          int sims, int n, int L, hipStream_t st);
-int search_result(const Tree& t, const SearchWs& w, const Slot* slots, Ctr* ctr, int sims, int n, hipStream_t st);
+// session: nn_rows and the counters take this call's rows and backups only (kv_search_continue)
+int search_result(const Tree& t, const SearchWs& w, const Slot* slots, Ctr* ctr, int sims, int n, bool session,
+                  hipStream_t st);
+// search sessions: play root edge edge[i] in tree i (-1: none), then the per-call reset of a continue
+int search_advance(const Tree& t, const SearchWs& w, Slot* slots, int8_t* boards, uint16_t* moves, int8_t* root_rows,
+                   const int* edge, int8_t* states, int n, Ctr* ctr, hipStream_t st);
+int search_resume(const Tree& t, const SearchWs& w, Slot* slots, uint32_t* np_mt, unsigned long long seed, int n,
+                  int L, hipStream_t st);
 
 }  // namespace kv

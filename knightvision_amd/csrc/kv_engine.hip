@@ -486,6 +486,12 @@ struct kv_engine {
     float* s_hlogits = nullptr;   // KV_EVAL_HASH: the full rows k_hash_eval writes for the leaf batch
     size_t s_hrows = 0;
     int* s_rem_host = nullptr;    // pinned: trees with done < sims, read back once per sim-step
+    // search session (kv_search_advance / kv_search_continue): the trees of the last kv_search; the host
+    // keeps each root's status, move count and visits from the last result or advance
+    int sess_n = 0;  // 0: no session
+    std::vector<kv::SessionSlot> sess_host;
+    std::vector<int> sess_done;
+    int* s_edge = nullptr;  // [slots]: the edges of the running advance
 };
 
 // order e->st after an outstanding device-to-device copy of the engine's buffers on a caller stream
@@ -888,7 +894,8 @@ static int search_reserve(kv_engine* e, int n, int L) {
     if (!w.ss) {
         if ((rc = search_alloc(w.ss, S)) || (rc = search_alloc(w.remaining, 1)) || (rc = search_alloc(w.res, S)) ||
             (rc = search_alloc(e->s_states, S * 80)) || (rc = search_alloc(e->s_rboards, RR * 64, true)) ||
-            (rc = search_alloc(e->s_rlogits, RR * 4096)) || (rc = search_alloc(e->s_rvalues, RR)))
+            (rc = search_alloc(e->s_rlogits, RR * 4096)) || (rc = search_alloc(e->s_rvalues, RR)) ||
+            (rc = search_alloc(w.sess, S, true)) || (rc = search_alloc(e->s_edge, S)))
             return rc;
         if (hipHostMalloc(&e->s_rem_host, sizeof(int)) != hipSuccess) {
             e->s_rem_host = nullptr;
@@ -913,6 +920,18 @@ static int search_reserve(kv_engine* e, int n, int L) {
     }
     if (L > 1 && !t.e_V && (rc = search_alloc(t.e_V, S * (size_t)t.ecap, true))) return rc;
     return KV_OK;
+}
+
+// the session of a finished kv_search / kv_search_continue: what the host keeps of every root
+static void session_note(kv_engine* e, const kv_search_result* out, int n) {
+    e->sess_host.assign(n, kv::SessionSlot{});
+    e->sess_done.assign(n, 0);
+    for (int i = 0; i < n; ++i) {
+        e->sess_host[i].status = out[i].status;
+        e->sess_host[i].n_moves = out[i].n_moves;
+        e->sess_done[i] = out[i].status == kv::SR_SEARCHED ? out[i].sims : 0;
+    }
+    e->sess_n = n;
 }
 
 // one network pass of a search (or the hash test evaluator): the root rows, or the step's leaf batch with
@@ -961,6 +980,7 @@ int kv_search(kv_engine* e, const int8_t* states, int n, const kv_search_params*
                    "squares 0..7, ep -1..7)", i);
     }
     e->used = 2;
+    e->sess_n = 0;  // a new session begins when this search has succeeded
     KV_HIP(hipSetDevice(e->cfg.device));
     const auto t0 = std::chrono::steady_clock::now();
     const int L = p->leaves, rows = n * L;
@@ -971,6 +991,7 @@ int kv_search(kv_engine* e, const int8_t* states, int n, const kv_search_params*
     hipStream_t st = e->st;
     // a search that overflowed a shrunk pool leaves the engine usable: the flag is this search's own
     KV_HIP(hipMemsetAsync(&e->ctr->error, 0, sizeof(int), st));
+    KV_HIP(hipMemsetAsync(w.sess, 0, (size_t)n * sizeof(kv::SessionSlot), st));
     KV_HIP(hipMemcpyAsync(e->s_states, states, (size_t)n * 80, hipMemcpyHostToDevice, st));
     if ((rc = kv::search_load(t, w, e->slots, e->boards, e->moves, e->s_rboards, e->np_mt, e->s_states, p->seed, n,
                               L, e->ctr, st)))
@@ -1003,12 +1024,154 @@ int kv_search(kv_engine* e, const int8_t* states, int n, const kv_search_params*
         KV_HIP(hipStreamSynchronize(st));
         if (*e->s_rem_host == 0) break;
     }
-    if ((rc = kv::search_result(t, w, e->slots, e->ctr, p->sims, n, st))) return rc;
+    if ((rc = kv::search_result(t, w, e->slots, e->ctr, p->sims, n, false, st))) return rc;
     KV_HIP(hipMemcpyAsync(out, w.res, (size_t)n * sizeof(kv_search_result), hipMemcpyDeviceToHost, st));
     KV_HIP(hipStreamSynchronize(st));
     e->steps += 1;
     e->wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return eng_counters(e);
+    if ((rc = eng_counters(e))) return rc;
+    session_note(e, out, n);
+    return KV_OK;
+}
+
+int kv_search_advance(kv_engine* e, int n, const int32_t* edge, int8_t* states_out) {
+    KV_REQUIRE(e, KV_EINVAL, "kv_search_advance: NULL argument");
+    KV_REQUIRE(e->sess_n > 0, KV_EINVAL, "kv_search_advance: no session (kv_search starts one)");
+    KV_REQUIRE(edge, KV_EINVAL, "kv_search_advance: NULL argument");
+    KV_REQUIRE(n == e->sess_n, KV_EINVAL, "kv_search_advance: %d trees, the session holds %d", n, e->sess_n);
+    // checked against the roots the host knows, so that a bad edge changes no tree
+    for (int i = 0; i < n; ++i) {
+        if (edge[i] < 0) continue;
+        const kv::SessionSlot& se = e->sess_host[i];
+        KV_REQUIRE(se.status == kv::SR_SEARCHED, KV_EINVAL,
+                   "kv_search_advance: edge %d at tree %d, whose root is not searched (status %d)", edge[i], i,
+                   se.status);
+        KV_REQUIRE(edge[i] < se.n_moves, KV_EINVAL, "kv_search_advance: edge %d at tree %d, whose root has %d moves",
+                   edge[i], i, se.n_moves);
+    }
+    KV_HIP(hipSetDevice(e->cfg.device));
+    const kv::SearchWs& w = e->sw;
+    hipStream_t st = e->st;
+    const int sess_n = e->sess_n;
+    e->sess_n = 0;  // back when the advance has succeeded
+    KV_HIP(hipMemsetAsync(&e->ctr->error, 0, sizeof(int), st));
+    KV_HIP(hipMemcpyAsync(e->s_edge, edge, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    int rc = kv::search_advance(e->tree, w, e->slots, e->boards, e->moves, e->s_rboards, e->s_edge, e->s_states, n,
+                                e->ctr, st);
+    if (rc) return rc;
+    std::vector<kv::SessionSlot> got(n);
+    KV_HIP(hipMemcpyAsync(got.data(), w.sess, (size_t)n * sizeof(kv::SessionSlot), hipMemcpyDeviceToHost, st));
+    if (states_out) KV_HIP(hipMemcpyAsync(states_out, e->s_states, (size_t)n * 80, hipMemcpyDeviceToHost, st));
+    KV_HIP(hipMemcpyAsync(e->ctr_host, e->ctr, sizeof(kv::Ctr), hipMemcpyDeviceToHost, st));
+    KV_HIP(hipStreamSynchronize(st));
+    if (e->ctr_host->error) {
+        kv::set_error("kv_search_advance: device error flags 0x%x (1: move list overflow; 32: the tree and the "
+                      "position after the move disagree)", e->ctr_host->error);
+        return e->ctr_host->error & 32 ? KV_EHIP : KV_EOVERFLOW;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (edge[i] < 0) continue;
+        e->sess_host[i] = got[i];
+        e->sess_done[i] = got[i].kept;
+    }
+    e->sess_n = sess_n;
+    return KV_OK;
+}
+
+int kv_search_continue(kv_engine* e, int n, const kv_search_params* p, kv_search_result* out, int32_t* kept) {
+    KV_REQUIRE(e, KV_EINVAL, "kv_search_continue: NULL argument");
+    KV_REQUIRE(e->sess_n > 0, KV_EINVAL, "kv_search_continue: no session (kv_search starts one)");
+    KV_REQUIRE(p && out, KV_EINVAL, "kv_search_continue: NULL argument");
+    KV_REQUIRE(n == e->sess_n, KV_EINVAL, "kv_search_continue: %d trees, the session holds %d", n, e->sess_n);
+    KV_REQUIRE(p->leaves >= 1 && p->leaves <= KV_MAX_LEAVES, KV_EINVAL,
+               "kv_search_continue: leaves %d out of range [1, %d]", p->leaves, KV_MAX_LEAVES);
+    KV_REQUIRE(p->sims >= 1 && p->sims <= e->cfg.sims, KV_EINVAL,
+               "kv_search_continue: sims %d out of range [1, %d] (the engine's sims size its tree pools)", p->sims,
+               e->cfg.sims);
+    KV_REQUIRE(p->alpha >= 2.2250738585072014e-308 && p->alpha < 1.0, KV_EINVAL,
+               "kv_search_continue: alpha must be a normal double in (0,1), got %g", p->alpha);
+    KV_REQUIRE(p->eps == 0.0, KV_EINVAL,
+               "kv_search_continue: eps %g, a session's roots take no Dirichlet noise (eps must be 0)", p->eps);
+    KV_HIP(hipSetDevice(e->cfg.device));
+    const auto t0 = std::chrono::steady_clock::now();
+    const int L = p->leaves, rows = n * L;
+    const int sess_n = e->sess_n;
+    e->sess_n = 0;  // back when the call has succeeded
+    int rc = search_reserve(e, n, L);
+    if (rc) return rc;
+    const kv::SearchWs& w = e->sw;
+    const kv::Tree& t = e->tree;
+    hipStream_t st = e->st;
+    // what the host knows of the roots: the dropped trees take a root row, the longest top-up bounds the steps
+    bool any_fresh = false;
+    int longest = 0;
+    for (int i = 0; i < n; ++i) {
+        const kv::SessionSlot& se = e->sess_host[i];
+        if (se.status != kv::SR_SEARCHED) continue;
+        any_fresh = any_fresh || se.fresh;
+        longest = std::max(longest, p->sims - (se.fresh ? 0 : e->sess_done[i]));
+        if (kept) kept[i] = se.fresh ? 0 : e->sess_done[i];
+    }
+    if (kept)
+        for (int i = 0; i < n; ++i)
+            if (e->sess_host[i].status != kv::SR_SEARCHED) kept[i] = 0;
+    KV_HIP(hipMemsetAsync(&e->ctr->error, 0, sizeof(int), st));
+    if ((rc = kv::search_resume(t, w, e->slots, e->np_mt, p->seed, n, L, st))) return rc;
+    if (any_fresh) {
+        // k_mcts_root on the dropped trees' rows, in the batch class of the whole call (kv_search)
+        const int root_rows = rows > 16 ? std::max(n, 17) : n;
+        if ((rc = search_eval(e, e->s_rboards, root_rows, false))) return rc;
+        kv::DevCfg dc = e->dc;
+        dc.slots = n;
+        dc.eps = 0.0;
+        dc.alpha = p->alpha;
+        if ((rc = kv::mcts_root(dc, t, e->slots, e->moves, e->s_rlogits, e->s_rvalues, e->probs, e->np_mt, e->ctr,
+                                st)))
+            return rc;
+    }
+    if (longest > 0) {
+        if ((rc = kv::search_select(t, w, e->slots, e->boards, e->ctr, p->sims, n, L, st))) return rc;
+        const bool counted = L > 1;  // kv_search's loop; with one leaf the longest top-up is the step count
+        for (int step = 0;; ++step) {
+            KV_REQUIRE(step < longest, KV_EHIP, "kv_search_continue: %d sim-steps without finishing %d sims", step,
+                       p->sims);
+            if ((rc = search_eval(e, w.lboards, rows, true))) return rc;
+            if (counted) KV_HIP(hipMemsetAsync(w.remaining, 0, sizeof(int), st));
+            if ((rc = kv::search_backup_select(t, w, e->slots, e->boards, e->ctr, p->sims, n, L, st))) return rc;
+            if (!counted) {
+                if (step + 1 == longest) break;
+                continue;
+            }
+            KV_HIP(hipMemcpyAsync(e->s_rem_host, w.remaining, sizeof(int), hipMemcpyDeviceToHost, st));
+            KV_HIP(hipStreamSynchronize(st));
+            if (*e->s_rem_host == 0) break;
+        }
+    }
+    if ((rc = kv::search_result(t, w, e->slots, e->ctr, p->sims, n, true, st))) return rc;
+    KV_HIP(hipMemcpyAsync(out, w.res, (size_t)n * sizeof(kv_search_result), hipMemcpyDeviceToHost, st));
+    KV_HIP(hipStreamSynchronize(st));
+    e->steps += 1;
+    e->wall_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if ((rc = eng_counters(e))) return rc;
+    session_note(e, out, sess_n);
+    return KV_OK;
+}
+
+int kv_search_tree_size(kv_engine* e, int i, int32_t* nodes, int32_t* edges) {
+    KV_REQUIRE(e && nodes && edges, KV_EINVAL, "kv_search_tree_size: NULL argument");
+    KV_REQUIRE(e->sess_n > 0, KV_EINVAL, "kv_search_tree_size: no session (kv_search starts one)");
+    KV_REQUIRE(i >= 0 && i < e->sess_n, KV_EINVAL, "kv_search_tree_size: tree %d, the session holds %d", i,
+               e->sess_n);
+    *nodes = *edges = 0;
+    const kv::SessionSlot& se = e->sess_host[i];
+    if (se.status != kv::SR_SEARCHED || se.fresh) return KV_OK;  // no tree (yet)
+    KV_HIP(hipSetDevice(e->cfg.device));
+    kv::MctsSlot m;
+    KV_HIP(hipMemcpyAsync(&m, e->ms + i, sizeof(m), hipMemcpyDeviceToHost, e->st));
+    KV_HIP(hipStreamSynchronize(e->st));
+    *nodes = m.node_count;
+    *edges = (m.edge_count + 15) & ~15;  // every block counted to its 16-edge boundary
+    return KV_OK;
 }
 
 size_t kv_sizeof_search_result(void) { return sizeof(kv_search_result); }
@@ -1148,7 +1311,7 @@ void kv_destroy(kv_engine* e) {
                     e->mc_logits, e->mc_values,
                     t.e_V, e->sw.ss, e->sw.lf, e->sw.paths, e->sw.lboards, e->sw.lmoves, e->sw.lcnt, e->sw.llogits,
                     e->sw.lvalues, e->sw.remaining, e->sw.res, e->s_states, e->s_rboards, e->s_rlogits,
-                    e->s_rvalues, e->s_hlogits};
+                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (e->ctr_host) (void)hipHostFree(e->ctr_host);

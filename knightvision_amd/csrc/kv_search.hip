@@ -16,6 +16,11 @@
 //            tree * L + j -> backup (expansions and W / N updates in j order,
 //            V back to 0). Backup of step k and select of step k + 1 are one launch.
 //   result : root visits, q, priors, best move, principal variation
+// A search session (kv_search_advance / kv_search_continue) follows a game:
+//   advance: play a root move; its child's subtree is packed to the front of the
+//            tree's pools in place (or the tree dropped when there is no child)
+//   resume : the per-call reset, then the sim-steps above up to the root's
+//            visit target, carried visits counting
 // The kernels are templated on HASV: without it (L = 1) no V is read or
 // written and every score is kv_mcts.hip's puct() itself, so the search is
 // the self-play one bit for bit.
@@ -240,7 +245,7 @@ __device__ inline void search_backup_tree(const Tree& t, const SearchWs& w, Ctr*
                     if (HASV) t.e_V[e] = 0;
                 }
                 if (lane == 0) {
-                    t.node[nb + m.node_count] = NodeRec{first, n, 0, 0};
+                    t.node[nb + m.node_count] = NodeRec{first, n, 0, __float_as_int(v)};
                     t.e_child[eb + lf.leaf_edge] = (uint16_t)m.node_count;
                 }
                 m.node_count += 1;
@@ -296,7 +301,8 @@ __global__ __launch_bounds__(64) void k_search_backup_select(Tree t, SearchWs w,
     search_select_tree<HASV>(t, w, slots, boards, ctr, sims, L, blockIdx.x);
 }
 
-__global__ __launch_bounds__(64) void k_search_result(Tree t, SearchWs w, const Slot* slots, Ctr* ctr, int sims) {
+__global__ __launch_bounds__(64) void k_search_result(Tree t, SearchWs w, const Slot* slots, Ctr* ctr, int sims,
+                                                      int session) {
     const int i = blockIdx.x, lane = threadIdx.x;
     const SearchSlot ss = w.ss[i];
     const MctsSlot m = t.ms[i];
@@ -350,15 +356,262 @@ __global__ __launch_bounds__(64) void k_search_result(Tree t, SearchWs w, const 
     o->best = searched ? bi : -1;
     o->pv_len = len;
     o->steps = ss.steps;
-    o->nn_rows = searched ? 1 + ss.leaf_rows : 0;
+    // a session's continue counts this call only: no root row for a carried tree, the new backups
+    const SessionSlot se = session ? w.sess[i] : SessionSlot{};
+    o->nn_rows = searched ? (session ? se.root_row : 1) + ss.leaf_rows : 0;
     o->pad = 0;
     o->root_value = searched ? m.root_value : ss.term_value;
     const int bN = searched ? t.e_N[eb + bi] : 0;
     o->best_q = bN > 0 ? t.e_W[eb + bi] / (float)bN : 0.0f;
     if (searched) {
-        atomicAdd(&ctr->sims, (unsigned long long)ss.done);
+        atomicAdd(&ctr->sims, (unsigned long long)(ss.done - (session ? se.kept : 0)));
         atomicAdd(&ctr->nn_rows, (unsigned long long)ss.leaf_rows);
     }
+}
+
+// ---- search sessions (DESIGN.md "Search sessions") ----
+// The kept set of a re-root is one bit per old node id in LDS (8 KB at KV_MAX_SIMS) with the count of kept
+// nodes below each 32-id word beside it, so the old id -> new id map is a rank query, new id = kept nodes
+// below the old id, and needs no table of ids.
+constexpr int KEEP_WORDS = 65536 / 32 + 2;  // a bit for every 16-bit child id, and the word a 64-id chunk reads past
+static_assert(KV_MAX_SIMS + 2 <= 65536, "node ids are 16-bit");
+
+__device__ inline int keep_rank(const uint32_t* keep, const int* below, int id) {
+    return below[id >> 5] + __popc(keep[id >> 5] & ((1u << (id & 31)) - 1u));
+}
+
+// the kept ids of the 64-id chunk at `base` that lie above chunk bit `b` (b = -1: all)
+__device__ inline uint64_t keep_chunk_above(const uint32_t* keep, int base, int b) {
+    const uint64_t mk = (uint64_t)keep[base >> 5] | ((uint64_t)keep[(base >> 5) + 1] << 32);
+    return b >= 63 ? 0ull : mk & (~0ull << (b + 1));
+}
+
+// Play root edge edge[i] in tree i: the slot's position becomes the one after the move (k_search_load's root
+// move generation), and the subtree of the edge's child is packed to the front of the tree's pools in place;
+// without a child the tree is dropped and the next continue builds a fresh root. One wavefront per tree.
+__global__ __launch_bounds__(64) void k_search_advance(Tree t, SearchWs w, Slot* slots, int8_t* boards,
+                                                       uint16_t* moves, int8_t* root_rows, const int* edge,
+                                                       int8_t* states, Ctr* ctr) {
+    __shared__ uint32_t keep[KEEP_WORDS];
+    __shared__ int below[KEEP_WORDS];
+    __shared__ int8_t bd[64];
+    __shared__ int s_meta[8];  // wtm wkr wkc bkr bkc flags ep
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const int k = edge[i];
+    if (k < 0) return;  // this tree stays as it is
+    const size_t eb = (size_t)i * t.ecap, nb = (size_t)i * t.ncap;
+    SearchSlot ss = w.ss[i];
+    MctsSlot m = t.ms[i];
+    Slot s = slots[i];
+    if (ss.status != SR_SEARCHED || k >= s.nmoves) {  // the host checked both against the last result
+        if (lane == 0) atomicOr(&ctr->error, 32);
+        return;
+    }
+    // a tree dropped by the advance before and not continued since has no node yet: dropped again
+    const bool built = w.sess[i].fresh == 0;
+    const uint16_t mv = moves[(size_t)i * MAXM + k];  // the root list is node 0's move words
+    const int c = built ? (int)t.e_child[eb + k] : (int)NO_CHILD;
+    const int played_n = built ? (int)t.e_N[eb + k] : 0;
+    // 1. the position after the move, as the oracle's make_valid_move gives it
+    bd[lane] = boards[(size_t)i * 64 + lane];
+    if (lane == 0) {
+        s_meta[0] = s.wtm; s_meta[1] = s.wkr; s_meta[2] = s.wkc; s_meta[3] = s.bkr; s_meta[4] = s.bkc;
+        s_meta[5] = s.flags; s_meta[6] = s.ep;
+    }
+    __syncthreads();
+    if (lane == 0) make_move_board(bd, s_meta[0], s_meta[1], s_meta[2], s_meta[3], s_meta[4], s_meta[5], s_meta[6], mv);
+    __syncthreads();
+    const int8_t code = bd[lane];
+    int8_t* so = states + (size_t)i * 80;
+    so[lane] = code;
+    if (lane < 16) {
+        const int fl = s_meta[5], ep = s_meta[6];
+        int8_t x = 0;
+        if (lane <= 4) x = (int8_t)s_meta[lane];
+        else if (lane <= 10) x = (int8_t)((fl >> (lane - 5)) & 1);  // F_WKM .. F_BRQ in vector order
+        else if (lane == 11) x = (int8_t)(ep < 0 ? -1 : ep >> 3);
+        else if (lane == 12) x = (int8_t)(ep < 0 ? -1 : ep & 7);
+        so[64 + lane] = x;
+    }
+    // 2. the new root's move list, keeping the board as getValidMoves leaves it (k_search_load)
+    Pos p = wave_pos(code, s_meta[0], s_meta[1], s_meta[2], s_meta[3], s_meta[4], s_meta[5], s_meta[6]);
+    const bool kings_only = __ballot(code != 0 && code != 1 && code != 7) == 0ull;
+    uint16_t* ml = moves + (size_t)i * MAXM;
+    int n = 0;
+    if (!kings_only) {
+        n = wave_valid_moves(p, ml, MAXM, lane);
+        if (n > MAXM && lane == 0) atomicOr(&ctr->error, 1);
+        n = n < MAXM ? n : MAXM;
+    }
+    const int8_t after = kings_only ? code : (int8_t)pos_at(p, lane);
+    boards[(size_t)i * 64 + lane] = after;
+    root_rows[(size_t)i * 64 + lane] = after;
+    const int status = kings_only ? SR_DRAW : n > 0 ? SR_SEARCHED : in_check(p) ? SR_CHECKMATED : SR_STALEMATE;
+    const bool carried = c != NO_CHILD;
+    int kept_nodes = 0, kept_edges = 0;
+    float root_value = 0.f;
+    if (carried) {
+        const int ncount = m.node_count;
+        // 3a. mark: one ascending pass over the old ids, a child's id being larger than its parent's
+        for (int x = lane; x < KEEP_WORDS; x += 64) keep[x] = 0;
+        __syncthreads();
+        if (lane == 0) keep[c >> 5] = 1u << (c & 31);
+        for (int base = c & ~63; base < ncount; base += 64) {
+            const NodeRec mine = base + lane < ncount ? t.node[nb + base + lane] : NodeRec{0, 0, 0, 0};
+            int b = -1;
+            for (;;) {
+                __syncthreads();  // the marks of the node before
+                const uint64_t mk = keep_chunk_above(keep, base, b);
+                if (mk == 0ull) break;
+                b = __ffsll((unsigned long long)mk) - 1;
+                if (base + b >= ncount) break;
+                const int first = __shfl(mine.first, b), cnt = __shfl(mine.cnt, b);
+                for (int j = lane; j < cnt; j += 64) {
+                    const int ch = t.e_child[eb + first + j];
+                    if (ch != NO_CHILD) atomicOr(&keep[ch >> 5], 1u << (ch & 31));
+                }
+            }
+        }
+        __syncthreads();
+        // 3b. renumber: kept nodes below every word, each lane summing a run of words
+        {
+            const int words = (ncount + 31) >> 5, per = (words + 63) >> 6;
+            const int w0 = min(lane * per, words), w1 = min(w0 + per, words);
+            int mine = 0;
+            for (int x = w0; x < w1; ++x) mine += __popc(keep[x]);
+            int total = 0;
+            int run = wave_excl_scan(mine, lane, total);
+            for (int x = w0; x < w1; ++x) {
+                below[x] = run;
+                run += __popc(keep[x]);
+            }
+            kept_nodes = total;
+        }
+        __syncthreads();
+        // 3c. move, in old id order: new id <= old id and new offset <= old offset, so a block only ever
+        // lands on places already read; each 64-edge chunk is read whole before it is written
+        int new_id = 0, edges = 0;
+        for (int base = c & ~63; base < ncount; base += 64) {
+            const NodeRec mine = base + lane < ncount ? t.node[nb + base + lane] : NodeRec{0, 0, 0, 0};
+            int b = -1;
+            for (;;) {
+                const uint64_t mk = keep_chunk_above(keep, base, b);
+                if (mk == 0ull) break;
+                b = __ffsll((unsigned long long)mk) - 1;
+                if (base + b >= ncount) break;
+                const int first = __shfl(mine.first, b), cnt = __shfl(mine.cnt, b), val = __shfl(mine.value, b);
+                const int nf = (edges + 15) & ~15;
+                for (int j0 = 0; j0 < cnt; j0 += 64) {
+                    const int j = j0 + lane;
+                    const bool in = j < cnt;
+                    const size_t eo = eb + first + (in ? j : 0);
+                    const uint16_t e_mv = t.e_move[eo], e_n = t.e_N[eo];
+                    const float e_p = t.e_P[eo], e_w = t.e_W[eo];
+                    const int ch = t.e_child[eo];
+                    __syncthreads();
+                    if (in) {
+                        const size_t en = eb + nf + j;
+                        t.e_move[en] = e_mv;
+                        t.e_P[en] = e_p;
+                        t.e_N[en] = e_n;
+                        t.e_W[en] = e_w;
+                        t.e_child[en] = ch == NO_CHILD ? NO_CHILD : (uint16_t)keep_rank(keep, below, ch);
+                    }
+                    __syncthreads();
+                }
+                if (new_id == 0) root_value = __int_as_float(val);
+                // the root's visit count is the played edge's: 1 + the sum of its own edges' (a fresh root's 1)
+                if (lane == 0) t.node[nb + new_id] = NodeRec{nf, cnt, new_id == 0 ? played_n : 0, val};
+                new_id += 1;
+                edges = nf + cnt;
+            }
+        }
+        kept_edges = edges;
+        __syncthreads();
+        // self-check: the regenerated root move list is node 0's
+        const NodeRec r0 = t.node[nb];
+        bool bad = status != SR_SEARCHED || r0.cnt != n || new_id != kept_nodes;
+        for (int j = lane; j < n && j < r0.cnt; j += 64) bad = bad || t.e_move[eb + r0.first + j] != ml[j];
+        if (__ballot(bad) != 0ull && lane == 0) atomicOr(&ctr->error, 32);
+    }
+    if (lane != 0) return;
+    ss.status = status;
+    ss.done = carried ? played_n - 1 : 0;
+    ss.vroot = 0;
+    ss.accepted = 0;
+    ss.steps = 0;
+    ss.leaf_rows = 0;
+    ss.term_value = status == SR_CHECKMATED ? (p.wtm ? -1.f : 1.f) : 0.f;
+    w.ss[i] = ss;
+    SessionSlot se = {};
+    se.status = status;
+    se.n_moves = n;
+    se.kept = carried ? played_n - 1 : 0;
+    se.fresh = carried ? 0 : 1;
+    w.sess[i] = se;
+    m.node_count = kept_nodes;  // 0 for a dropped tree until its root is built
+    m.edge_count = kept_edges;
+    if (carried) {
+        m.root_value = root_value;
+        m.root_wtm = p.wtm;
+    }
+    t.ms[i] = m;
+    s.status = ST_IDLE;  // k_search_resume hands the fresh roots to k_mcts_root
+    s.ply = 0;
+    s.wtm = p.wtm;
+    s.wkr = p.wkr; s.wkc = p.wkc; s.bkr = p.bkr; s.bkc = p.bkc;
+    s.flags = p.flags;
+    s.ep = p.ep;
+    s.nmoves = n;
+    slots[i] = s;
+}
+
+// The per-call reset of a continue: the call's own counters, the carried visits, and for a dropped tree
+// what k_search_load prepares for k_mcts_root.
+__global__ __launch_bounds__(64) void k_search_resume(Tree t, SearchWs w, Slot* slots, uint32_t* np_mt,
+                                                      unsigned long long seed, int L) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    SearchSlot ss = w.ss[i];
+    SessionSlot se = w.sess[i];
+    const bool searched = ss.status == SR_SEARCHED;
+    const bool fresh = se.fresh != 0 && searched;
+    for (int j = lane; j < L; j += 64) w.lcnt[(size_t)i * L + j] = 0;
+    const int n = slots[i].nmoves;
+    if (fresh && t.e_V)
+        for (int j = lane; j < n; j += 64) t.e_V[(size_t)i * t.ecap + j] = 0;
+    if (lane != 0) return;
+    if (fresh) ss.done = 0;
+    ss.vroot = 0;
+    ss.accepted = 0;
+    ss.steps = 0;
+    ss.leaf_rows = 0;
+    w.ss[i] = ss;
+    se.status = ss.status;
+    se.n_moves = searched ? n : 0;
+    se.kept = searched ? ss.done : 0;
+    se.fresh = 0;
+    se.root_row = fresh ? 1 : 0;
+    w.sess[i] = se;
+    Slot s = slots[i];
+    s.status = fresh ? ST_ACTIVE : ST_IDLE;  // k_mcts_root takes the active slots
+    if (fresh) s.rows_total += 1;            // the root's network row (kv_stats.nn_rows)
+    slots[i] = s;
+    if (fresh) mt_seed_genrand(np_mt + (size_t)i * MT_WORDS, (uint32_t)(seed + (unsigned long long)i));
+}
+
+int search_advance(const Tree& t, const SearchWs& w, Slot* slots, int8_t* boards, uint16_t* moves, int8_t* root_rows,
+                   const int* edge, int8_t* states, int n, Ctr* ctr, hipStream_t st) {
+    hipLaunchKernelGGL(k_search_advance, dim3(n), dim3(64), 0, st, t, w, slots, boards, moves, root_rows, edge, states,
+                       ctr);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
+}
+
+int search_resume(const Tree& t, const SearchWs& w, Slot* slots, uint32_t* np_mt, unsigned long long seed, int n,
+                  int L, hipStream_t st) {
+    hipLaunchKernelGGL(k_search_resume, dim3(n), dim3(64), 0, st, t, w, slots, np_mt, seed, L);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
 }
 
 int search_load(const Tree& t, const SearchWs& w, Slot* slots, int8_t* boards, uint16_t* moves, int8_t* root_rows,
@@ -391,8 +644,9 @@ int search_backup_select(const Tree& t, const SearchWs& w, const Slot* slots, co
     return KV_OK;
 }
 
-int search_result(const Tree& t, const SearchWs& w, const Slot* slots, Ctr* ctr, int sims, int n, hipStream_t st) {
-    hipLaunchKernelGGL(k_search_result, dim3(n), dim3(64), 0, st, t, w, slots, ctr, sims);
+int search_result(const Tree& t, const SearchWs& w, const Slot* slots, Ctr* ctr, int sims, int n, bool session,
+                  hipStream_t st) {
+    hipLaunchKernelGGL(k_search_result, dim3(n), dim3(64), 0, st, t, w, slots, ctr, sims, session ? 1 : 0);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }

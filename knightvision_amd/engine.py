@@ -204,7 +204,38 @@ class PositionSearch:
         p = _lib.SearchParams(sims=int(sims), leaves=int(leaves), eps=float(eps), alpha=float(alpha), seed=int(seed))
         _lib.check(_lib.lib().kv_search(self.h, st.ctypes.data_as(C.POINTER(C.c_int8)), len(st), C.byref(p),
                                         out.ctypes.data_as(C.POINTER(_lib.SearchResult))), "kv_search")
+        self._n = len(st)
         return out
+
+    # -- search sessions (include/kv.h): the trees of the last search() follow a game
+    def advance(self, edges) -> np.ndarray:
+        """Play root move edges[i] (root list index, -1: none) in every tree of the last search: the child's
+        subtree becomes the tree; an edge the search never expanded drops it -> the [n, 80] states after the
+        moves."""
+        ed = np.ascontiguousarray(edges, dtype=np.int32).reshape(-1)
+        out = np.zeros((len(ed), 80), dtype=np.int8)
+        _lib.check(_lib.lib().kv_search_advance(self.h, len(ed), ed.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                out.ctypes.data_as(C.POINTER(C.c_int8))), "kv_search_advance")
+        return out
+
+    def resume(self, sims, leaves=1, alpha=0.3, seed=0):
+        """Search the session's current roots up to `sims` root visits, the carried visits counting ->
+        (SEARCH_DTYPE[n] with steps / nn_rows of this call only, kept[n]: the visits each root already held)."""
+        n = getattr(self, "_n", 0)
+        out = np.zeros(n, dtype=SEARCH_DTYPE)
+        kept = np.zeros(n, dtype=np.int32)
+        p = _lib.SearchParams(sims=int(sims), leaves=int(leaves), eps=0.0, alpha=float(alpha), seed=int(seed))
+        _lib.check(_lib.lib().kv_search_continue(self.h, n, C.byref(p),
+                                                 out.ctypes.data_as(C.POINTER(_lib.SearchResult)),
+                                                 kept.ctypes.data_as(C.POINTER(C.c_int32))), "kv_search_continue")
+        return out, kept
+
+    def tree_size(self, i):
+        """(nodes, edges of the pool in use) of the session's tree i."""
+        nodes, edges = C.c_int32(), C.c_int32()
+        _lib.check(_lib.lib().kv_search_tree_size(self.h, int(i), C.byref(nodes), C.byref(edges)),
+                   "kv_search_tree_size")
+        return nodes.value, edges.value
 
     def calibration(self) -> dict:
         c = _lib.Calib()

@@ -39,6 +39,40 @@ def search_move(gs, searcher, sims=800, leaves=32):
     return valid[int(row["best"])]
 
 
+class SearchSession:
+    """A game followed by one search tree (engine.PositionSearch's session calls): the subtree under every
+    move played is searched on at the next best_move() instead of being rebuilt. Both sides' moves go through
+    push(); a move the search never expanded simply starts a fresh tree."""
+
+    def __init__(self, gs, searcher, sims=800, leaves=32):
+        self.gs, self.searcher, self.sims, self.leaves = gs, searcher, sims, leaves
+        self.row = None    # the last search result of the current position
+        self.kept = 0      # root visits the last best_move() found already there
+        self._live = False  # the searcher's session stands at gs's position
+
+    def best_move(self):
+        """The search's move for the current position (search_move's rule), None at a root that is not
+        searched; the first call searches the position, later ones resume its tree."""
+        valid = self.gs.getValidMoves()
+        if self._live:
+            rows, kept = self.searcher.resume(self.sims, leaves=self.leaves)
+            self.row, self.kept = rows[0], int(kept[0])
+        else:
+            self.row, self.kept = self.searcher.search(self.gs._state()[None], self.sims, leaves=self.leaves)[0], 0
+            self._live = True
+        if self.row["status"] != 0:
+            return None
+        return valid[int(self.row["best"])]
+
+    def push(self, move):
+        """Play `move` (an entry of gs.getValidMoves()) on the game and in the tree."""
+        index = self.gs.getValidMoves().index(move)
+        if self._live:
+            self.searcher.advance([index])
+        self.gs.makeMove(move)
+        self.row = None
+
+
 def masked_argmax_move(logits: torch.Tensor, legal_indices) -> int:
     """stockfish_play.py:64-84: argmax of the logits restricted to the legal
     move indices (encode_move), -1 when there are none."""

@@ -203,7 +203,8 @@ typedef struct {
     int algo;             /* KV_ALGO_* of the network convs */
     int tree_edge_cap;    /* MCTS edges per slot; <= 0: KV_MAXM x (sims + 1), which cannot overflow. An
                              expansion that does not fit raises KV_EOVERFLOW (kv_stats.tree_overflows) */
-    int keep_root_visits; /* 1: keep each MCTS move's root visit counts (pi) for kv_root_visits[_device] */
+    int keep_root_visits; /* 1: keep each MCTS move's root visit counts (pi) for kv_root_visits[_device];
+                             2: as 1, and also each committed move's root move words for kv_root_moves[_device] */
 } kv_config;
 
 #define KV_MAXM 320 /* move-list capacity per position */
@@ -285,6 +286,15 @@ int kv_root_visits(kv_engine* e, int32_t* out, size_t cap, size_t* n);
  * [n][KV_MAXM] in the engine's record order -- row k belongs to record k of kv_records_device (0xffff past the
  * position's move list); stream as in kv_records_device */
 int kv_root_visits_device(kv_engine* e, uint16_t* out_dev, size_t cap, size_t* n, void* stream);
+/* The root move list those counts are indexed by (keep_root_visits = 2): out uint16 [n][KV_MAXM], entry j the
+ * move word (from | to << 6 | flags << 12, as kv_search_result.moves) of count j, 0xffff past the list; rows in
+ * kv_records' order, the same permutation as kv_root_visits. The policy logit of a word w is
+ * (w & 63) * 64 + ((w >> 6) & 63) (kv_net_forward_boards_legal). On an engine created with keep_root_visits 0
+ * or 1: KV_EINVAL. */
+int kv_root_moves(kv_engine* e, uint16_t* out, size_t cap, size_t* n);
+/* the same words device to device in the engine's record order (row k belongs to record k of kv_records_device
+ * and row k of kv_root_visits_device); stream as in kv_records_device */
+int kv_root_moves_device(kv_engine* e, uint16_t* out_dev, size_t cap, size_t* n, void* stream);
 int kv_sync(kv_engine* e);
 void kv_destroy(kv_engine* e);
 
@@ -518,6 +528,25 @@ int kv_tr_head1x1_backward_f16(const void* h_dev, const void* dout_dev, int rows
                                float* dw_dev, float* db_dev, void* ws_dev, size_t ws_bytes, void* stream);
 /* encode_board planes fp32 [n][12][8][8] (ai/ai.py:17-30) -> NHWC fp16 [n][64][cpad], channels >= 12 zero */
 int kv_tr_planes_to_nhwc(const float* planes_dev, int n, int cpad, void* out_dev, void* stream);
+/* Soft-target policy loss on MCTS root visit distributions (no reference counterpart: the reference trains on
+ * the move played). logits fp16 [B][4096], 16-byte aligned; the targets are a CSR over the whole dataset:
+ * off int64 [N + 1], idx / cnt uint16 [nnz], one entry per legal root move (policy index (w & 63) * 64 +
+ * ((w >> 6) & 63) of its move word w, visit count), and row [B] names the dataset row of each batch row
+ * (0 <= row[i] < N and idx < 4096 are the caller's to guarantee; an entry with idx >= 4096 is skipped). Per batch
+ * row, with z the logits widened to fp32, p = softmax(z) and pi_k = (sum of cnt with idx k) / (sum of the row's
+ * cnt), 0 for a row whose counts are all 0:
+ *   lse = max + log sum exp(z - max), ce = -sum_k pi_k (z_k - lse), ent = lse - sum_k p_k z_k.
+ * Every output is bit-reproducible and independent of B and of the row's place in the batch. */
+int kv_tr_policy_loss_f16(const void* logits_dev, const int64_t* row_dev, const int64_t* off_dev,
+                          const uint16_t* idx_dev, const uint16_t* cnt_dev, int B, float* ce_dev, float* ent_dev,
+                          float* lse_dev, void* stream);
+/* its backward from the forward's lse / ent and the per-row gradients gce / gent of ce / ent (they carry the
+ * means, the entropy coefficient and the loss scale), s = sum_k pi_k (1 or 0):
+ *   dlogits_k = fp16(gce (s p_k - pi_k) - gent p_k ((z_k - lse) + ent)), computed in fp32, rounded once */
+int kv_tr_policy_loss_backward_f16(const void* logits_dev, const int64_t* row_dev, const int64_t* off_dev,
+                                   const uint16_t* idx_dev, const uint16_t* cnt_dev, int B, const float* lse_dev,
+                                   const float* ent_dev, const float* gce_dev, const float* gent_dev,
+                                   void* dlogits_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -119,6 +119,8 @@ def _declare(L):
         "kv_stats_get": ([vp, P(Stats)], i),
         "kv_root_visits": ([vp, P(C.c_int32), sz, P(sz)], i),
         "kv_root_visits_device": ([vp, vp, sz, P(sz), vp], i),
+        "kv_root_moves": ([vp, P(C.c_uint16), sz, P(sz)], i),
+        "kv_root_moves_device": ([vp, vp, sz, P(sz), vp], i),
         "kv_records_device": ([vp, vp, sz, P(sz), vp], i),
         "kv_sync": ([vp], i),
         "kv_reset_records": ([vp], i),
@@ -162,6 +164,8 @@ def _declare(L):
         "kv_tr_head1x1_f16": ([vp, i, vp, vp, vp, vp], i),
         "kv_tr_head1x1_workspace": ([i], sz),
         "kv_tr_head1x1_backward_f16": ([vp, vp, i, vp, vp, vp, vp, vp, sz, vp], i),
+        "kv_tr_policy_loss_f16": ([vp, vp, vp, vp, vp, i, vp, vp, vp, vp], i),
+        "kv_tr_policy_loss_backward_f16": ([vp, vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp], i),
     }
     for name, (args, res) in sig.items():
         if not hasattr(L, name):
@@ -176,7 +180,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_net_forward_boards", "kv_net_forward_boards_legal", "kv_net_set_timing", "kv_net_last_timing", "kv_net_destroy", "kv_net_set_precision", "kv_net_set_algo",
             "kv_net_calibration", "kv_engine_calibration",
             "kv_create",
-            "kv_load_weights", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_root_visits", "kv_root_visits_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
+            "kv_load_weights", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
             "kv_search", "kv_sizeof_search_result", "kv_search_advance", "kv_search_continue", "kv_search_tree_size",
             "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm",
             "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_i8gemm_bench",
@@ -185,7 +189,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_tr_conv3x3_f16", "kv_tr_conv3x3_add_f16", "kv_tr_conv_weights_f16", "kv_tr_wgrad_workspace", "kv_tr_conv3x3_wgrad_f16",
             "kv_tr_bn_workspace", "kv_tr_bn_stats_f16", "kv_tr_bn_apply_f16", "kv_tr_bn_backward_f16",
             "kv_tr_channel_sum_f16", "kv_tr_planes_to_nhwc", "kv_tr_head1x1_f16", "kv_tr_head1x1_workspace",
-            "kv_tr_head1x1_backward_f16"]
+            "kv_tr_head1x1_backward_f16", "kv_tr_policy_loss_f16", "kv_tr_policy_loss_backward_f16"]
 
 
 def lib():

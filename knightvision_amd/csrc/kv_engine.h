@@ -134,6 +134,7 @@ struct Tree {  // per-slot SoA edge pools + node records, slot i at i*ecap / i*n
     float c_puct;
     int sims;
     uint16_t* e_V;  // position search with several leaves in flight (kv_search.hip): descents in flight per edge
+    uint16_t* root_moves;  // optional [record_cap][MAXM]: the root's move words beside root_visits, 0xffff padded
 };
 
 // ---- position search (kv_search.hip): per-tree state, per-(tree, j) descents of the running sim-step ----

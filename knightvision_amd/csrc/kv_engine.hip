@@ -649,6 +649,7 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
         ALLOC(e->probs, S * 4096 * sizeof(float));
         ALLOC(e->sqrt_tab, (size_t)(t.ncap + 2) * sizeof(float));
         if (cfg->keep_root_visits) ALLOC(t.root_visits, (size_t)e->cfg.record_cap * kv::MAXM * sizeof(uint16_t));
+        if (cfg->keep_root_visits == 2) ALLOC(t.root_moves, (size_t)e->cfg.record_cap * kv::MAXM * sizeof(uint16_t));
         const char* mc_env = getenv("KV_MCTS_COMPACT");  // "0": always the full-slot leaf batch (A/B timing)
         if (cfg->eval_mode != KV_EVAL_HASH && S > 1 && !(mc_env && mc_env[0] == '0')) {
             ALLOC(e->mc_slot_of, S * sizeof(int));
@@ -1297,6 +1298,44 @@ int kv_root_visits_device(kv_engine* e, uint16_t* out_dev, size_t cap, size_t* n
     return eng_note_copy(e, (hipStream_t)stream);
 }
 
+int kv_root_moves(kv_engine* e, uint16_t* out, size_t cap, size_t* n) {
+    KV_REQUIRE(e && n, KV_EINVAL, "kv_root_moves: NULL argument");
+    KV_REQUIRE(e->tree.root_moves, KV_EINVAL, "kv_root_moves: engine was created without keep_root_visits = 2");
+    int rc = eng_counters(e);
+    if (rc) return rc;
+    const size_t cnt = (size_t)std::min<unsigned long long>(e->ctr_host->rec_count, (unsigned long long)e->cfg.record_cap);
+    *n = cnt;
+    if (!out) return KV_OK;
+    KV_REQUIRE(cap >= cnt, KV_EINVAL, "kv_root_moves: buffer holds %zu records, need %zu", cap, cnt);
+    std::vector<kv_record> rec(cnt);
+    std::vector<uint16_t> mv(cnt * kv::MAXM);
+    KV_HIP(hipMemcpy(rec.data(), e->rec, cnt * sizeof(kv_record), hipMemcpyDeviceToHost));
+    KV_HIP(hipMemcpy(mv.data(), e->tree.root_moves, mv.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    std::vector<size_t> ord(cnt);
+    for (size_t k = 0; k < cnt; ++k) ord[k] = k;
+    std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {  // kv_records' order, as kv_root_visits
+        return rec[a].game_id != rec[b].game_id ? rec[a].game_id < rec[b].game_id : rec[a].ply < rec[b].ply;
+    });
+    for (size_t k = 0; k < cnt; ++k)
+        memcpy(out + k * kv::MAXM, mv.data() + ord[k] * kv::MAXM, kv::MAXM * sizeof(uint16_t));
+    return KV_OK;
+}
+
+int kv_root_moves_device(kv_engine* e, uint16_t* out_dev, size_t cap, size_t* n, void* stream) {
+    KV_REQUIRE(e && n, KV_EINVAL, "kv_root_moves_device: NULL argument");
+    KV_REQUIRE(e->tree.root_moves, KV_EINVAL,
+               "kv_root_moves_device: engine was created without keep_root_visits = 2");
+    int rc = eng_counters(e);
+    if (rc) return rc;
+    const size_t cnt = (size_t)std::min<unsigned long long>(e->ctr_host->rec_count, (unsigned long long)e->cfg.record_cap);
+    *n = cnt;
+    if (!out_dev) return KV_OK;
+    KV_REQUIRE(cap >= cnt, KV_EINVAL, "kv_root_moves_device: buffer holds %zu records, need %zu", cap, cnt);
+    KV_HIP(hipMemcpyAsync(out_dev, e->tree.root_moves, cnt * kv::MAXM * sizeof(uint16_t), hipMemcpyDeviceToDevice,
+                          (hipStream_t)stream));
+    return eng_note_copy(e, (hipStream_t)stream);
+}
+
 void kv_destroy(kv_engine* e) {
     if (!e) return;
     (void)hipSetDevice(e->cfg.device);
@@ -1311,7 +1350,7 @@ void kv_destroy(kv_engine* e) {
                     e->mc_logits, e->mc_values,
                     t.e_V, e->sw.ss, e->sw.lf, e->sw.paths, e->sw.lboards, e->sw.lmoves, e->sw.lcnt, e->sw.llogits,
                     e->sw.lvalues, e->sw.remaining, e->sw.res, e->s_states, e->s_rboards, e->s_rlogits,
-                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge};
+                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (e->ctr_host) (void)hipHostFree(e->ctr_host);

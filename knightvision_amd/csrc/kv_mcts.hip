@@ -305,6 +305,10 @@ __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* sl
     if (t.root_visits && (long long)ridx < cfg.record_cap) {
         uint16_t* rv = t.root_visits + (size_t)ridx * MAXM;
         for (int j = lane; j < MAXM; j += 64) rv[j] = j < n ? t.e_N[eb + j] : (uint16_t)0xffff;
+        if (t.root_moves) {
+            uint16_t* rm = t.root_moves + (size_t)ridx * MAXM;
+            for (int j = lane; j < MAXM; j += 64) rm[j] = j < n ? t.e_move[eb + j] : (uint16_t)0xffff;
+        }
     }
     if (lane == 0) slots[i] = s;
 }

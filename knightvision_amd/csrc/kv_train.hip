@@ -757,6 +757,143 @@ __global__ void planes_to_nhwc_kernel(const float* __restrict__ planes, int n, i
     out[i] = c < 12 ? (_Float16)planes[(b * 12 + c) * 64 + sq] : (_Float16)0.f;
 }
 
+// ---------------------------------------------------------- policy loss --
+// Soft-target policy loss of the learn loop's "visits" mode (DESIGN.md "Training on the search's
+// visit distribution"): per batch row the cross-entropy of softmax(z) against the root visit
+// distribution pi of the row's dataset sample, and the softmax's entropy, from the fp16 logits
+// z [B][4096] widened to fp32. The targets are the dataset-wide CSR (off / idx / cnt, one entry per
+// legal root move, uint16 policy index and visit count) and row[i] names batch row i's sample, so no
+// per-batch target is built. One 256-thread workgroup per row, a thread holds logits
+// tid*8 .. tid*8+7 and 2048+tid*8 .. +7 (two 16-B loads). Every sum is taken in a fixed order
+// (16 terms in the thread, an xor butterfly in the wave, the 4 waves in order): a row's outputs are
+// bit-reproducible and do not depend on B or on the row's place in the batch.
+//   forward : mx = max z, d_k = z_k - mx, S = sum exp(d_k), lse = mx + log S,
+//             ent = log S - (sum exp(d_k) d_k) / S, ce = (sum_j cnt_j (log S - d_idx_j)) / sum_j cnt_j
+//             (0 for a row whose counts are all 0)
+//   backward: p_k = exp(z_k - lse), pi_k from integer counts added per index in a 16-KB LDS row (u32 LDS
+//             atomics: exact, so order-free), dz_k = fp16(gce (s p_k - pi_k) - gent p_k ((z_k - lse) + ent))
+namespace pl {
+constexpr int NL = 4096, THREADS = 256;
+}
+
+__device__ inline float pl_wave_sum(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// sums a[0], a[1] over the workgroup (to every thread); red is this call's own [4][2]
+__device__ inline void pl_block_sum2(float (&a)[2], float (*red)[2]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    a[0] = pl_wave_sum(a[0]);
+    a[1] = pl_wave_sum(a[1]);
+    if (lane == 0) {
+        red[w][0] = a[0];
+        red[w][1] = a[1];
+    }
+    __syncthreads();
+    a[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
+    a[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
+}
+
+__device__ inline unsigned pl_block_sum_u32(unsigned v, unsigned* red) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += (unsigned)__shfl_xor((int)v, m);
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ __launch_bounds__(pl::THREADS) void policy_loss_fwd_kernel(
+    const _Float16* __restrict__ logits, const long long* __restrict__ row, const long long* __restrict__ off,
+    const uint16_t* __restrict__ idx, const uint16_t* __restrict__ cnt, float* __restrict__ ce,
+    float* __restrict__ ent, float* __restrict__ lse) {
+    __shared__ float red_mx[4];
+    __shared__ float red_s[4][2], red_t[4][2];
+    __shared__ unsigned red_n[4];
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const _Float16* zr = logits + (size_t)i * pl::NL;
+    float z[16];
+    h8_to_f(*(const u32x4*)(zr + tid * 8), z);
+    h8_to_f(*(const u32x4*)(zr + pl::NL / 2 + tid * 8), z + 8);
+    float mx = z[0];
+#pragma unroll
+    for (int e = 1; e < 16; ++e) mx = fmaxf(mx, z[e]);
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m));
+    if (lane == 0) red_mx[w] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red_mx[0], red_mx[1]), fmaxf(red_mx[2], red_mx[3]));
+    float a[2] = {0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const float d = z[e] - mx, ex = expf(d);
+        a[0] += ex;
+        a[1] += ex * d;  // exp(d) = 0 exactly long before d reaches -131,008 (the fp16 range): never 0 * inf
+    }
+    pl_block_sum2(a, red_s);
+    const float log_s = logf(a[0]);  // a[0] >= 1: the maximum's own term
+    const long long r = row[i], o0 = off[r], o1 = off[r + 1];
+    float b[2] = {0.f, 0.f};
+    unsigned n = 0;
+    for (long long j = o0 + tid; j < o1; j += pl::THREADS) {
+        const unsigned k = idx[j], c = cnt[j];
+        if (k >= (unsigned)pl::NL) continue;
+        n += c;
+        b[0] += (float)c * (log_s - ((float)zr[k] - mx));
+    }
+    pl_block_sum2(b, red_t);
+    const unsigned total = pl_block_sum_u32(n, red_n);
+    if (tid == 0) {
+        lse[i] = mx + log_s;
+        ent[i] = log_s - a[1] / a[0];
+        ce[i] = total ? b[0] / (float)total : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(pl::THREADS) void policy_loss_bwd_kernel(
+    const _Float16* __restrict__ logits, const long long* __restrict__ row, const long long* __restrict__ off,
+    const uint16_t* __restrict__ idx, const uint16_t* __restrict__ cnt, const float* __restrict__ lse,
+    const float* __restrict__ ent, const float* __restrict__ gce, const float* __restrict__ gent,
+    _Float16* __restrict__ dlogits) {
+    __shared__ __attribute__((aligned(16))) unsigned pc[pl::NL];
+    __shared__ unsigned red_n[4];
+    const int i = blockIdx.x, tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < pl::NL / pl::THREADS; ++q) pc[q * pl::THREADS + tid] = 0u;
+    __syncthreads();
+    const long long r = row[i], o0 = off[r], o1 = off[r + 1];
+    unsigned n = 0;
+    for (long long j = o0 + tid; j < o1; j += pl::THREADS) {
+        const unsigned k = idx[j], c = cnt[j];
+        if (k >= (unsigned)pl::NL) continue;
+        n += c;
+        atomicAdd(&pc[k], c);
+    }
+    const unsigned total = pl_block_sum_u32(n, red_n);  // its barrier also orders the LDS atomics
+    const float ftot = (float)total, s = total ? 1.f : 0.f;
+    const float l = lse[i], h = ent[i], g1 = gce[i], g2 = gent[i];
+    const _Float16* zr = logits + (size_t)i * pl::NL;
+    _Float16* dr = dlogits + (size_t)i * pl::NL;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const int k0 = half * (pl::NL / 2) + tid * 8;
+        float z[8];
+        h8_to_f(*(const u32x4*)(zr + k0), z);
+        const u32x4 c0 = *(const u32x4*)(pc + k0), c1 = *(const u32x4*)(pc + k0 + 4);
+        const unsigned c[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+        h8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float lp = z[e] - l, p = expf(lp);
+            const float pi = total ? (float)c[e] / ftot : 0.f;
+            o[e] = (_Float16)(g1 * (s * p - pi) - g2 * p * (lp + h));
+        }
+        *(h8*)(dr + k0) = o;
+    }
+}
+
 }  // namespace tr
 }  // namespace kv
 
@@ -974,6 +1111,34 @@ int kv_tr_planes_to_nhwc(const float* planes_dev, int n, int cpad, void* out_dev
     const size_t total = (size_t)n * 64 * cpad;
     hipLaunchKernelGGL(planes_to_nhwc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        planes_dev, n, cpad, (_Float16*)out_dev);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
+}
+
+int kv_tr_policy_loss_f16(const void* logits_dev, const int64_t* row_dev, const int64_t* off_dev,
+                          const uint16_t* idx_dev, const uint16_t* cnt_dev, int B, float* ce_dev, float* ent_dev,
+                          float* lse_dev, void* stream) {
+    KV_REQUIRE(logits_dev && row_dev && off_dev && ce_dev && ent_dev && lse_dev && B > 0, KV_EINVAL,
+               "kv_tr_policy_loss_f16: bad arguments");
+    KV_REQUIRE(((uintptr_t)logits_dev & 15) == 0, KV_EINVAL, "kv_tr_policy_loss_f16: logits must be 16-byte aligned");
+    hipLaunchKernelGGL(policy_loss_fwd_kernel, dim3(B), dim3(pl::THREADS), 0, (hipStream_t)stream,
+                       (const _Float16*)logits_dev, (const long long*)row_dev, (const long long*)off_dev, idx_dev,
+                       cnt_dev, ce_dev, ent_dev, lse_dev);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
+}
+
+int kv_tr_policy_loss_backward_f16(const void* logits_dev, const int64_t* row_dev, const int64_t* off_dev,
+                                   const uint16_t* idx_dev, const uint16_t* cnt_dev, int B, const float* lse_dev,
+                                   const float* ent_dev, const float* gce_dev, const float* gent_dev,
+                                   void* dlogits_dev, void* stream) {
+    KV_REQUIRE(logits_dev && row_dev && off_dev && lse_dev && ent_dev && gce_dev && gent_dev && dlogits_dev && B > 0,
+               KV_EINVAL, "kv_tr_policy_loss_backward_f16: bad arguments");
+    KV_REQUIRE((((uintptr_t)logits_dev | (uintptr_t)dlogits_dev) & 15) == 0, KV_EINVAL,
+               "kv_tr_policy_loss_backward_f16: logits and dlogits must be 16-byte aligned");
+    hipLaunchKernelGGL(policy_loss_bwd_kernel, dim3(B), dim3(pl::THREADS), 0, (hipStream_t)stream,
+                       (const _Float16*)logits_dev, (const long long*)row_dev, (const long long*)off_dev, idx_dev,
+                       cnt_dev, lse_dev, ent_dev, gce_dev, gent_dev, (_Float16*)dlogits_dev);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }

@@ -123,7 +123,8 @@ def unpack_pi(counts: torch.Tensor, packed: torch.Tensor, maxm: int) -> torch.Te
     return out
 
 
-def gather_experience(records, games, dst: int | None = 0, pi=None, force_collective: bool = False):
+def gather_experience(records, games, dst: int | None = 0, pi=None, force_collective: bool = False,
+                      pi_moves=None):
     """End-of-iteration gather of every rank's (records, games), ordered by
     (game_id, ply) / game_id. `records` is a numpy RECORD_DTYPE array or the
     engine's device tensor (SelfPlayEngine.records_device(), uint8 [n, 80]);
@@ -134,11 +135,16 @@ def gather_experience(records, games, dst: int | None = 0, pi=None, force_collec
     record's legal-move prefix (pack_pi: 2 B per legal move + a 2-B count) and
     is re-padded on the receiver. Returns numpy arrays on `dst` (every rank
     when dst is None) and Nones elsewhere: (records, games), or (records,
-    games, pi uint16 [n, MAXM]) when pi is given."""
+    games, pi uint16 [n, MAXM]) when pi is given. `pi_moves` (with pi:
+    SelfPlayEngine.root_moves_device(), the root move words the counts are
+    indexed by, 0xffff padded alike) travels in the same compact prefix form
+    and adds a fourth array, moves uint16 [n, MAXM] in record order."""
     fc = force_collective
     r = gather_rows(_as_rows(records, RECORD_DTYPE), dst, fc)
     g = gather_rows(_as_rows(games, GAME_DTYPE), dst, fc)
-    p = None
+    p = m = None
+    if pi_moves is not None and pi is None:
+        raise ValueError("gather_experience: pi_moves goes with pi (the counts those move words index)")
     if pi is not None:
         maxm = pi.shape[-1] // 2
         counts, packed = pack_pi(pi)
@@ -148,8 +154,16 @@ def gather_experience(records, games, dst: int | None = 0, pi=None, force_collec
         if c_all is not None:
             p = unpack_pi(c_all.contiguous().view(torch.int16).reshape(-1),
                           k_all.contiguous().view(torch.int16).reshape(-1), maxm)
+        if pi_moves is not None:
+            m_counts, m_packed = pack_pi(pi_moves)
+            if not torch.equal(m_counts, counts):
+                raise ValueError("gather_experience: a row's move words and visit counts differ in length")
+            m_all = gather_rows(m_packed.view(torch.uint8).reshape(-1, 2), dst, fc)  # the prefix lengths are pi's
+            if c_all is not None:
+                m = unpack_pi(c_all.contiguous().view(torch.int16).reshape(-1),
+                              m_all.contiguous().view(torch.int16).reshape(-1), maxm)
     if r is None:
-        return (None, None) if pi is None else (None, None, None)
+        return (None,) * (2 + (pi is not None) + (pi_moves is not None))
     order = record_order(r) if r.shape[0] else None
     r = (r[order] if order is not None else r).cpu().numpy()
     gms = g.cpu().numpy().reshape(-1).view(GAME_DTYPE) if g.numel() else np.zeros(0, GAME_DTYPE)
@@ -157,8 +171,11 @@ def gather_experience(records, games, dst: int | None = 0, pi=None, force_collec
     gms = gms[np.argsort(gms["game_id"], kind="stable")]
     if pi is None:
         return recs, gms
-    p = (p[order] if order is not None else p).cpu().numpy()
-    return recs, gms, np.ascontiguousarray(p).view(np.uint16).reshape(p.shape[0], -1)
+    out = [recs, gms]
+    for x in (p, m) if pi_moves is not None else (p,):
+        x = (x[order] if order is not None else x).cpu().numpy()
+        out.append(np.ascontiguousarray(x).view(np.uint16).reshape(x.shape[0], -1))
+    return tuple(out)
 
 
 def pi_wire_bytes(pi) -> int:

@@ -38,20 +38,22 @@ class SelfPlayEngine:
     def __init__(self, weights, *, slots=256, n_games=256, seed=42, seed_mode=SEED_PER_GAME, max_moves=None,
                  batch=16, eps=0.25, alpha=0.3, sims=0, c_puct=1.5, eval_mode=EVAL_FAITHFUL, record_cap=None,
                  recycle=True, device=0, game_id_base=0, game_id_stride=1, precision="fp32",
-                 algo="auto", tree_edge_cap=0, keep_root_visits=False):
+                 algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False):
         L = _lib.lib()
+        keep = 2 if keep_root_moves else (1 if keep_root_visits else 0)  # the move words imply the visits
         if record_cap is None:
             # one record per committed ply: a capped game holds at most max_moves; an uncapped one
             # (the reference default) is given 1,024 plies (its random-init games run 116-660). A
             # run that still fills the buffer fails with KV_EOVERFLOW ("record buffer full").
             per_game = int(max_moves) if max_moves else 1024
-            record_cap = max(1 << 16, min(1 << (22 if keep_root_visits else 27), int(n_games) * per_game))
+            # (the side buffers are 640 B per record each: 2^22 records with the visits, 2^21 with the moves too)
+            record_cap = max(1 << 16, min(1 << {0: 27, 1: 22, 2: 21}[keep], int(n_games) * per_game))
         cfg = _lib.Config(device=device, slots=slots, n_games=n_games, game_id_base=game_id_base,
                           game_id_stride=game_id_stride, seed=seed, seed_mode=seed_mode,
                           max_moves=max_moves if max_moves else 0, batch=batch, eps=eps, alpha=alpha, sims=sims,
                           c_puct=c_puct, eval_mode=eval_mode, record_cap=record_cap, recycle=1 if recycle else 0,
                           precision=PRECISIONS[precision], algo=ALGOS[algo],
-                          tree_edge_cap=int(tree_edge_cap), keep_root_visits=1 if keep_root_visits else 0)
+                          tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep)
         h = C.c_void_p()
         _lib.check(L.kv_create(C.byref(cfg), C.byref(h)), "kv_create")
         self.h = h
@@ -123,6 +125,34 @@ class SelfPlayEngine:
         if n.value:
             _lib.check(L.kv_root_visits(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)),
                        "kv_root_visits")
+        return out
+
+    def root_moves(self) -> np.ndarray:
+        """The root move words [records, MAXM] uint16 (from | to << 6 | flags << 12, 0xffff padded) the counts of
+        root_visits() are indexed by, rows in records() order (needs keep_root_moves=True). The policy logit
+        of a word w is (w & 63) * 64 + ((w >> 6) & 63)."""
+        L = _lib.lib()
+        n = C.c_size_t()
+        _lib.check(L.kv_root_moves(self.h, None, 0, C.byref(n)), "kv_root_moves")
+        out = np.zeros((n.value, _lib.MAXM), dtype=np.uint16)
+        if n.value:
+            _lib.check(L.kv_root_moves(self.h, out.ctypes.data_as(C.POINTER(C.c_uint16)), n.value, C.byref(n)),
+                       "kv_root_moves")
+        return out
+
+    def root_moves_device(self):
+        """The same move words as a uint8 CUDA tensor [n, MAXM * 2], row k belonging to row k of
+        records_device() and of root_visits_device() (needs keep_root_moves=True)."""
+        import torch
+        L = _lib.lib()
+        n = C.c_size_t()
+        _lib.check(L.kv_root_moves_device(self.h, None, 0, C.byref(n), None), "kv_root_moves_device")
+        dev = torch.device("cuda", self.cfg.device)
+        out = torch.empty((n.value, _lib.MAXM * 2), dtype=torch.uint8, device=dev)
+        if n.value:
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(L.kv_root_moves_device(self.h, C.c_void_p(out.data_ptr()), n.value, C.byref(n),
+                                              C.c_void_p(st)), "kv_root_moves_device")
         return out
 
     def games(self) -> np.ndarray:

@@ -23,6 +23,13 @@ count -- W x (batch_size // W) rows per micro-batch, one optimizer step per
 accumulate_steps micro-batches, as on one process. Self-play game g of iteration i has the global id
 i * games_per_iter + g and the seeds SEED + id (per-game seeding).
 
+policy_target="visits" (no reference counterpart; MCTS self-play only) trains
+the policy on each record's root visit distribution instead of the move
+played: the engine keeps the root move words beside the visit counts, the
+dataset tuple carries them as sparse PolicyTargets (policy_targets.py) and
+the update step scores them with the fused HIP loss (train_ops.policy_loss).
+The default, "move", is the reference's loss.
+
 Not reproduced (out of the self-play path): the Stockfish
 evaluation, checkpoints, Telegram and TensorBoard logging.
 """
@@ -32,11 +39,13 @@ import math
 import os
 import time
 
+import numpy as np
 import torch
 
 from . import train as T
 from .distributed import gather_rows
 from .engine import SelfPlayEngine, packed_from
+from .policy_targets import PolicyTargets
 from .self_play import ALPHA, BATCH_SIZE as SELFPLAY_BATCH, EPSILON, SEED
 
 # learn.py's configuration (:105-112) and train.py's scheduler constants (:21, :463-464)
@@ -58,23 +67,31 @@ def _dist():
 
 
 def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_moves=None, slots=256,
-                   precision="fp32"):
+                   precision="fp32", policy_targets=False):
     """This rank's share of one iteration's games, played by the HIP engine with
-    the model's current weights. Returns (records, games) numpy arrays."""
+    the model's current weights. Returns (records, games) numpy arrays; with
+    policy_targets (MCTS runs) also the root visit counts and root move words of
+    every record, (records, games, visits uint16 [n, MAXM], moves uint16
+    [n, MAXM]) row for row, 0xffff past each position's move list."""
     dist, rank, world = _dist()
     dev = torch.device(device)
     ids = list(range(rank, n_games, world))
+    if policy_targets and sims <= 0:
+        raise ValueError("selfplay_shard: policy_targets needs the search's visit counts (sims > 0)")
     if not ids:
-        return None, None
+        return (None, None, None, None) if policy_targets else (None, None)
     base = iteration * n_games + rank
     from .self_play import batched_eval_mode
     with SelfPlayEngine(packed_from(model), slots=min(slots, len(ids)), n_games=len(ids), seed=SEED,
                         max_moves=max_moves, batch=SELFPLAY_BATCH, eps=EPSILON, alpha=ALPHA, sims=sims,
                         game_id_base=base, game_id_stride=world, device=dev.index or 0,
-                        precision=precision, eval_mode=batched_eval_mode() if sims == 0 else 0) as eng:
+                        precision=precision, eval_mode=batched_eval_mode() if sims == 0 else 0,
+                        keep_root_moves=bool(policy_targets)) as eng:
         eng.run()
         selfplay_shard.last_calibration = eng.calibration()  # the conv paths these weights ran on
         selfplay_shard.last_stats = eng.stats()
+        if policy_targets:
+            return eng.records(), eng.games(), eng.root_visits().astype("uint16"), eng.root_moves()
         return eng.records(), eng.games()
 
 
@@ -93,29 +110,65 @@ def rank_batch_size(batch_size: int, world: int) -> int:
     return max(1, batch_size // world)
 
 
-def decisive_filter(codes, moves, rewards):
+def decisive_filter(codes, moves, rewards, targets=None):
     """generate_self_play_data (self_play.py:304-310): keep only records whose
-    reward is +-1 when there are at least 10 of them."""
+    reward is +-1 when there are at least 10 of them (`targets`: the samples'
+    PolicyTargets rows, filtered with them)."""
     dec = rewards.abs() == 1.0
     if int(dec.sum()) >= 10:
-        return codes[dec], moves[dec], rewards[dec]
-    return codes, moves, rewards
+        out = codes[dec], moves[dec], rewards[dec]
+        return out if targets is None else out + (targets[dec],)
+    return (codes, moves, rewards) if targets is None else (codes, moves, rewards, targets)
 
 
-def extend_dataset(data, recs, games, dev):
+def _gather_targets(recs, games, pi, dev) -> PolicyTargets:
+    """This iteration's visit targets of every rank, in gather_rows' rank order (the order the samples'
+    tensors take): each row's legal-move prefix (distributed.pack_pi) of the visit counts and of the move
+    words crosses ranks, and the CSR is built from that compact form directly."""
+    if recs is not None and len(recs):
+        if pi is None:
+            raise ValueError("extend_dataset: policy_targets needs the records' (visits, moves) of selfplay_shard")
+        keep = np.isin(recs["game_id"], games["game_id"])  # records_to_tensors' rows: the finished games'
+        local = PolicyTargets.from_engine(pi[0][keep], pi[1][keep], dev)
+    else:
+        local = PolicyTargets.empty(dev)
+    counts = local.lengths().to(torch.int16)
+
+    def all_ranks(t):  # int16 travels as byte pairs (gloo has no int16 collectives)
+        return gather_rows(t.view(torch.uint8).reshape(-1, 2), dst=None).to(dev).contiguous().view(torch.int16).reshape(-1)
+
+    counts, idx, cnt = all_ranks(counts), all_ranks(local.idx), all_ranks(local.cnt)
+    off = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=dev)
+    off[1:] = torch.cumsum(counts.to(torch.int64) & 0xffff, 0)
+    return PolicyTargets(off, idx, cnt)
+
+
+def extend_dataset(data, recs, games, dev, pi=None, policy_targets=False):
     """dataset.extend(generate_self_play_data(...)) for one iteration
     (learn.py:194-199): the ranks' new records are all-gathered (the one
     end-of-iteration exchange) and filtered as one dataset (the reference's
     global decisive filter); every rank appends the same union, so every rank
     holds the whole dataset (64 + 12 B per sample) and the 90/10 split below is
-    the same on all of them."""
+    the same on all of them.
+    policy_targets ("visits" mode): `pi` is this rank's (visits, moves) of
+    selfplay_shard, row for row with `recs` (None on a rank without games); the
+    visit targets are gathered and filtered with the samples and the dataset
+    tuple carries them as a fourth element, samples that came without a search
+    holding their one-hot row."""
     if recs is not None and len(recs):
         local = T.records_to_tensors(recs, games, dev)
     else:
         local = (torch.zeros((0, 64), dtype=torch.int8, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
                  torch.zeros(0, dtype=torch.float32, device=dev))
-    union = decisive_filter(*(gather_rows(x, dst=None).to(dev) for x in local))
-    return union if data is None else tuple(torch.cat([a, b]) for a, b in zip(data, union))
+    if not policy_targets:
+        union = decisive_filter(*(gather_rows(x, dst=None).to(dev) for x in local))
+        return union if data is None else tuple(torch.cat([a, b]) for a, b in zip(data, union))
+    union = tuple(gather_rows(x, dst=None).to(dev) for x in local)
+    union = decisive_filter(*union, _gather_targets(recs, games, pi, dev))
+    if data is None:
+        return union
+    old = data[3] if len(data) > 3 else PolicyTargets.one_hot(data[1])
+    return tuple(torch.cat([a, b]) for a, b in zip(data[:3], union[:3])) + (PolicyTargets.cat([old, union[3]]),)
 
 
 def split_train_val(n: int, gen: torch.Generator):
@@ -133,7 +186,8 @@ def evaluate_sharded(model, data, idx, batch_size: int, dev) -> float:
     mine = idx[rank::world].to(dev)
     tot = torch.zeros(2, dtype=torch.float64, device=dev)
     if mine.numel():
-        batches = list(T.batches(*(x[mine] for x in data), batch_size, False))
+        batches = list(T.batches(*(x[mine] for x in data[:3]), batch_size, False,
+                                 targets=data[3][mine] if len(data) > 3 else None))
         n = sum(b.boards.shape[0] for b in batches)
         tot[0] = T.evaluate(model, batches) * n
         tot[1] = n
@@ -164,10 +218,12 @@ def train_with_validation(ddp, model, optimizer, data, epochs: int, batch_size: 
     scaler = T.make_scaler(dev)
     cos, plateau, step = make_lr_schedulers(optimizer)
     best, no_improve, ep, val_loss, done = math.inf, 0, None, math.inf, 0
-    shard = tuple(x[mine] for x in data)
+    shard = tuple(x[mine] for x in data[:3])
+    shard_targets = data[3][mine] if len(data) > 3 else None  # "visits" mode: this rank's rows of the CSR
     lrs = []
     for epoch in range(epochs):
-        ep = T.train_one_epoch(ddp, T.batches(*shard, rank_batch_size(batch_size, world), True, gen, total=n_max),
+        ep = T.train_one_epoch(ddp, T.batches(*shard, rank_batch_size(batch_size, world), True, gen, total=n_max,
+                                              targets=shard_targets),
                                optimizer, scaler, accumulate_steps=accumulate_steps)
         val_loss = evaluate_sharded(model, data, va, batch_size, dev)
         plateau.step(val_loss)
@@ -198,12 +254,23 @@ def make_lr_schedulers(optimizer):
 def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, epochs: int = TRAIN_EPOCHS,
                        batch_size: int = LEARN_BATCH_SIZE, lr: float = LEARN_LR,
                        accumulate_steps: int = T.ACCUM_STEPS, sims: int = 0, max_moves=None, slots: int = 256,
-                       seed: int = 0, games_path: str | None = None, max_samples: int = 10000, log=print):
+                       seed: int = 0, games_path: str | None = None, max_samples: int = 10000, log=print,
+                       policy_target: str = "move"):
     """Run the loop (learn.py reinforcement_loop :152-209); returns per-iteration statistics.
     `model` is a knightvision_amd.model.ChessNet (same parameters as ai/model.py) on `device`.
     `games_path`: the reference's JSONL dataset (ChessPGNDataset, :162) the self-play records extend --
     each sample keeps its own source's plane order and move indexing, as in the reference; None:
-    self-play records only (iteration 1 then has nothing to train on)."""
+    self-play records only (iteration 1 then has nothing to train on).
+    `policy_target`: "move" (the reference's loss: cross-entropy against the move played) or "visits"
+    (no reference counterpart): the policy trains on each self-play record's MCTS root visit distribution
+    (soft cross-entropy, PolicyTargets + train_ops.policy_loss), which needs sims > 0; the samples of
+    `games_path` then carry their one-hot rows."""
+    if policy_target not in ("move", "visits"):
+        raise ValueError(f"reinforcement_loop: policy_target {policy_target!r}: 'move' or 'visits'")
+    visits = policy_target == "visits"
+    if visits and sims <= 0:
+        raise ValueError("reinforcement_loop: policy_target='visits' trains on the search's root visit counts: "
+                         "sims must be > 0")
     _, rank, world = _dist()
     dev = torch.device(device)
     model.to(dev)
@@ -214,9 +281,11 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
     data = None  # (codes, moves, rewards) on the device: the whole dataset, on every rank
     if games_path is not None:
         data = T.ChessPGNDataset(games_path, max_samples=max_samples).materialize(dev)
+        if visits:
+            data = data + (PolicyTargets.one_hot(data[1]),)
     stats = []
     for it in range(iterations):
-        st = {"iteration": it + 1}
+        st = {"iteration": it + 1, "policy_target": policy_target}
         n = int(data[0].shape[0]) if data is not None else 0
         if n >= 2 * world:  # every rank holds train data (fewer samples: no update this iteration)
             t0 = time.perf_counter()
@@ -230,7 +299,13 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
                       train_split=tv["train_split"], val_split=tv["val_split"], lr=tv["lr"])
         model.eval()
         t0 = time.perf_counter()
-        recs, games = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves, slots=slots)
+        pi = None
+        if visits:
+            recs, games, *pi = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves,
+                                              slots=slots, policy_targets=True)
+            pi = None if recs is None else tuple(pi)
+        else:
+            recs, games = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves, slots=slots)
         st["selfplay_s"] = time.perf_counter() - t0
         cal = getattr(selfplay_shard, "last_calibration", None)
         if cal is not None:  # fp32 AUTO: the self-play network's conv path for this iteration's weights
@@ -242,7 +317,8 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
         if es is not None:  # this rank's engine: plies and MCTS simulations (the throughput a path flip moves)
             st.update(plies=int(es["plies"]), sims=int(es["sims"]))
         model.train()
-        data = extend_dataset(data, recs, games, dev)
+        data = extend_dataset(data, recs, games, dev, pi=pi, policy_targets=True) if visits \
+            else extend_dataset(data, recs, games, dev)
         st.update(records=int(data[0].shape[0]) if data is not None else 0,
                   games=int(len(games)) if games is not None else 0)
         if rank == 0 and log:

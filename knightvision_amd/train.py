@@ -58,6 +58,8 @@ class Batch:
     boards: torch.Tensor    # [B,12,8,8] fp32
     moves: torch.Tensor     # [B] int64
     outcomes: torch.Tensor  # [B] fp32
+    targets: "PolicyTargets | None" = None  # policy_targets.PolicyTargets: the sparse visit targets the batch
+    rows: torch.Tensor | None = None        # was drawn from, and the batch rows' rows of it ([B] int64)
 
 
 def records_to_tensors(records: np.ndarray, games: np.ndarray, device) -> tuple:
@@ -74,11 +76,14 @@ def records_to_tensors(records: np.ndarray, games: np.ndarray, device) -> tuple:
 
 
 def batches(codes, moves, rewards, batch_size: int, shuffle: bool, generator: torch.Generator | None = None,
-            total: int | None = None):
+            total: int | None = None, targets=None):
     """DataLoader(batch_size, shuffle) over the tensors (train.py:238-249). With
     `total` > len (data-parallel ranks holding unequal shards) the epoch order
     wraps around to `total` samples, so every rank runs the same number of
-    equal batches (DistributedSampler's padding)."""
+    equal batches (DistributedSampler's padding). `targets`: the samples'
+    PolicyTargets (row for row with `codes`); every batch then carries them
+    and its own sample indices, and batch_loss trains on the visit
+    distributions instead of the move played."""
     n = codes.shape[0]
     order = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
     if total is not None and total > n:
@@ -86,7 +91,10 @@ def batches(codes, moves, rewards, batch_size: int, shuffle: bool, generator: to
     order = order.to(codes.device)
     for i in range(0, order.numel(), batch_size):
         ix = order[i:i + batch_size]
-        yield Batch(codes_to_planes_t(codes[ix]), moves[ix], rewards[ix])
+        if targets is None:
+            yield Batch(codes_to_planes_t(codes[ix]), moves[ix], rewards[ix])
+        else:
+            yield Batch(codes_to_planes_t(codes[ix]), moves[ix], rewards[ix], targets, ix)
 
 
 # MIOpen selects convolution solutions per input shape (≈0.85 s for each new
@@ -109,7 +117,10 @@ def _pad_rows(model, x, bucket):
 
 def batch_loss(model, b: Batch, entropy_coef: float = ENTROPY_COEF, amp: bool = True, bucket: int | None = None):
     """The reference's per-batch loss (train.py:161-176): returns
-    (loss, loss_policy, loss_value, entropy, policy_logits)."""
+    (loss, loss_policy, loss_value, entropy, policy_logits). A batch that carries
+    PolicyTargets (Batch.targets / rows) replaces the policy term by the mean soft
+    cross-entropy against the visit distributions, the entropy coming from the same
+    fused op (train_ops.policy_loss); no reference counterpart."""
     dev_type = b.boards.device.type
     if bucket is None:
         bucket = ROW_BUCKET if dev_type == "cuda" else 0
@@ -118,6 +129,13 @@ def batch_loss(model, b: Batch, entropy_coef: float = ENTROPY_COEF, amp: bool = 
         pol, val = model(x, n_real) if n_real is not None else model(x)
     if n_real is not None:
         pol, val = pol[:n_real], val[:n_real]
+    if b.targets is not None:
+        from .train_ops import policy_loss
+        ce, ent = policy_loss(pol, b.targets, b.rows)
+        loss_policy, entropy = ce.mean(), ent.mean()
+        loss_value = F.mse_loss(val.squeeze().float(), b.outcomes)
+        loss = loss_policy + loss_value - entropy_coef * entropy
+        return loss, loss_policy, loss_value, entropy, pol
     loss_policy = F.cross_entropy(pol.float(), b.moves)
     loss_value = F.mse_loss(val.squeeze().float(), b.outcomes)
     logp = F.log_softmax(pol.float(), dim=1)
@@ -181,14 +199,20 @@ def train_one_epoch(model, data, optimizer, scaler, accumulate_steps: int = ACCU
 @torch.no_grad()
 def evaluate(model, data) -> float:
     """evaluate (train.py:109-124): mean of (CE + MSE) over samples, eval-mode
-    forward (the HIP tower for knightvision_amd.ChessNet)."""
+    forward (the HIP tower for knightvision_amd.ChessNet). Batches that carry
+    PolicyTargets are scored against them (the soft cross-entropy the update
+    trains on) instead of the move played."""
     model = model.module if hasattr(model, "module") else model  # DDP wrapper: evaluate the local replica
     was = model.training
     model.eval()
     tot, cnt = 0.0, 0
     for b in data:
         pol, val = model(b.boards)
-        lp = F.cross_entropy(pol.float(), b.moves)
+        if b.targets is not None:  # the target the update trains on
+            from .train_ops import policy_loss
+            lp = policy_loss(pol, b.targets, b.rows)[0].mean()
+        else:
+            lp = F.cross_entropy(pol.float(), b.moves)
         lv = F.mse_loss(val.squeeze().float(), b.outcomes)
         tot += float(lp + lv) * b.boards.shape[0]
         cnt += b.boards.shape[0]

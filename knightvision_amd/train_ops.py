@@ -246,6 +246,63 @@ class Head1x1(torch.autograd.Function):
         return dh, dw[:2].reshape(2, 512, 1, 1), db[:2].clone(), dw[2:].reshape(1, 512, 1, 1), db[2:].clone()
 
 
+class PolicyLoss(torch.autograd.Function):
+    """Per-row soft-target cross-entropy and softmax entropy of fp16 logits [B, 4096] against the dataset's
+    sparse visit targets (kv_tr_policy_loss_f16): (ce [B], ent [B]) fp32. The backward is one kernel from
+    the per-row gradients of both outputs, rounded to fp16 once."""
+
+    @staticmethod
+    def forward(ctx, logits, rows, off, idx, cnt):
+        logits = logits.contiguous()
+        rows = rows.to(device=logits.device, dtype=torch.int64).contiguous()
+        B = logits.shape[0]
+        ce = torch.empty(B, dtype=torch.float32, device=logits.device)
+        ent, lse = torch.empty_like(ce), torch.empty_like(ce)
+        _lib.check(_lib.lib().kv_tr_policy_loss_f16(logits.data_ptr(), rows.data_ptr(), off.data_ptr(),
+                                                    _ptr(idx), _ptr(cnt), B, ce.data_ptr(), ent.data_ptr(),
+                                                    lse.data_ptr(), _stream(logits)), "kv_tr_policy_loss_f16")
+        ctx.save_for_backward(logits, rows, off, idx, cnt, lse, ent)
+        return ce, ent
+
+    @staticmethod
+    def backward(ctx, gce, gent):
+        logits, rows, off, idx, cnt, lse, ent = ctx.saved_tensors
+        B = logits.shape[0]
+        gce = torch.zeros_like(lse) if gce is None else gce.to(torch.float32).contiguous()
+        gent = torch.zeros_like(lse) if gent is None else gent.to(torch.float32).contiguous()
+        dz = torch.empty_like(logits)
+        _lib.check(_lib.lib().kv_tr_policy_loss_backward_f16(
+            logits.data_ptr(), rows.data_ptr(), off.data_ptr(), _ptr(idx), _ptr(cnt), B, lse.data_ptr(),
+            ent.data_ptr(), gce.data_ptr(), gent.data_ptr(), dz.data_ptr(), _stream(logits)),
+            "kv_tr_policy_loss_backward_f16")
+        return dz, None, None, None, None
+
+
+def policy_loss_dense(logits: torch.Tensor, targets, rows: torch.Tensor, dtype=torch.float32):
+    """The torch restatement of PolicyLoss on a dense [B, 4096] target (any device and dtype)."""
+    z = logits.to(dtype)
+    pi = targets.dense(rows, dtype=dtype)
+    logp = torch.log_softmax(z, dim=1)
+    return -(pi * logp).sum(dim=1), -(torch.softmax(z, dim=1) * logp).sum(dim=1)
+
+
+def policy_loss(logits: torch.Tensor, targets, rows: torch.Tensor):
+    """(ce [B], ent [B]) of logits [B, 4096] against rows `rows` of the PolicyTargets `targets`
+    (policy_targets.py): ce_i = -sum_k pi_k log_softmax(z)_k, ent_i the entropy of softmax(z). CUDA fp16
+    logits (the autocast update step) run the HIP kernels; any other dtype or device runs the dense torch
+    restatement. The means, the entropy coefficient and the loss scale stay the caller's."""
+    if logits.dim() != 2 or logits.shape[1] != 4096 or rows.numel() != logits.shape[0]:
+        raise ValueError(f"policy_loss: logits {tuple(logits.shape)} / rows {tuple(rows.shape)}: need [B, 4096] / [B]")
+    if logits.is_cuda and logits.dtype == torch.float16:
+        if targets.device != logits.device:
+            raise ValueError(f"policy_loss: targets on {targets.device}, logits on {logits.device}")
+        if logits.shape[0] == 0:
+            z = logits.sum(1).float()
+            return z, z.clone()
+        return PolicyLoss.apply(logits, rows, targets.off, targets.idx, targets.cnt)
+    return policy_loss_dense(logits, targets, rows)
+
+
 def update_running_stats(bn: torch.nn.BatchNorm2d, mean: torch.Tensor, var: torch.Tensor, count: int):
     """nn.BatchNorm2d's running-statistics update from a training batch of `count` values per channel."""
     if not bn.track_running_stats:

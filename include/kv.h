@@ -205,10 +205,21 @@ typedef struct {
                              expansion that does not fit raises KV_EOVERFLOW (kv_stats.tree_overflows) */
     int keep_root_visits; /* 1: keep each MCTS move's root visit counts (pi) for kv_root_visits[_device];
                              2: as 1, and also each committed move's root move words for kv_root_moves[_device] */
+    int reuse_tree;       /* MCTS self-play (sims >= 1): 0: every ply's tree is built from nothing; 1: the subtree
+                             under the move just played is carried into the next ply (DESIGN.md "MCTS semantics",
+                             "Carried subtrees in self-play"): its visits count toward sims, the root takes the
+                             fresh root's mixed priors from the same numpy stream. Any other value, or 1 with
+                             sims 0: KV_EINVAL */
 } kv_config;
 
 #define KV_MAXM 320 /* move-list capacity per position */
 #define KV_MAX_SIMS 65000 /* MCTS edges keep 16-bit visit counts and child node ids */
+/* reuse_tree: inside a ply the compact leaf batch of the slots still searching is rebuilt at every sim-step
+ * whose live count is lower than at the last rebuild by at least this many slots (1: every change; DESIGN.md
+ * "Carried subtrees in self-play" records the measurement) */
+#ifndef KV_REUSE_COMPACT_STEP /* (a build may set another value to measure it) */
+#define KV_REUSE_COMPACT_STEP 1
+#endif
 
 typedef struct {
     int64_t game_id;
@@ -233,7 +244,7 @@ typedef struct {
     int64_t plies;        /* moves committed */
     int64_t games_done;
     int64_t nn_rows;      /* boards evaluated by the network */
-    int64_t sims;         /* MCTS backups completed */
+    int64_t sims;         /* MCTS backups completed (reuse_tree: a ply adds its new backups, not cfg.sims) */
     int64_t records;
     double res_conv_ms;   /* device time of the measured dominant-kernel launches (HIP events):
                              direct: the 10 residual convs of each forward; Winograd: one
@@ -250,6 +261,11 @@ typedef struct {
                                (the rest as 64x128 tiles in a second one; 100: one launch); 0 otherwise */
     char dom_kernel[96];    /* the name of the kernel those launches ran, as the library chose it (template
                                arguments included, e.g. "wino88i32_gemm_lagt_kernel<512,5>") */
+    int64_t sims_kept;      /* reuse_tree: root visits carried into plies, summed over the committed plies
+                               (sims + sims_kept == plies x cfg.sims) */
+    int64_t roots_carried;  /* reuse_tree: committed plies whose root was a carried tree */
+    int64_t leaf_batch_rows; /* rows of every MCTS leaf batch the network ran in kv_run, padding included, full
+                               and compact batches alike (with reuse_tree 0 too) */
 } kv_stats;
 
 typedef struct kv_engine kv_engine;
@@ -277,6 +293,9 @@ int kv_games(kv_engine* e, kv_game* out, size_t cap, size_t* n);
 /* drop the records collected so far (between kv_run calls) */
 int kv_reset_records(kv_engine* e);
 int kv_stats_get(kv_engine* e, kv_stats* out);
+/* sizeof(kv_config) / sizeof(kv_stats) as the library was built, for a binding to check its mirror against */
+size_t kv_sizeof_config(void);
+size_t kv_sizeof_stats(void);
 /* MCTS root visit counts of every committed move (keep_root_visits = 1):
  * out [n][KV_MAXM] in root move-list order, -1 padded, rows in kv_records'
  * order. No reference counterpart (the reference has no search); used by the

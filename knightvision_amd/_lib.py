@@ -21,7 +21,7 @@ class Config(C.Structure):
                 ("max_moves", C.c_int), ("batch", C.c_int), ("eps", C.c_double), ("alpha", C.c_double),
                 ("sims", C.c_int), ("c_puct", C.c_float), ("eval_mode", C.c_int), ("record_cap", C.c_int64),
                 ("recycle", C.c_int), ("precision", C.c_int), ("algo", C.c_int), ("tree_edge_cap", C.c_int),
-                ("keep_root_visits", C.c_int)]
+                ("keep_root_visits", C.c_int), ("reuse_tree", C.c_int)]
 
 
 class Record(C.Structure):
@@ -39,7 +39,8 @@ class Stats(C.Structure):
                 ("sims", C.c_int64), ("records", C.c_int64), ("res_conv_ms", C.c_double),
                 ("res_conv_launches", C.c_int64), ("step_ms", C.c_double), ("dom_flop", C.c_double),
                 ("dom_algo", C.c_int64), ("tree_overflows", C.c_int64), ("nn_rows_lazy", C.c_int64),
-                ("dom_path", C.c_int64), ("dom_split", C.c_int64), ("dom_kernel", C.c_char * 96)]
+                ("dom_path", C.c_int64), ("dom_split", C.c_int64), ("dom_kernel", C.c_char * 96),
+                ("sims_kept", C.c_int64), ("roots_carried", C.c_int64), ("leaf_batch_rows", C.c_int64)]
 
 
 NPATH = 10  # KV_NPATH
@@ -72,6 +73,7 @@ PGN_OUTCOME_NONE = -128
 MAXM = 320  # KV_MAXM, move-list capacity per position
 
 MAX_LEAVES = 64  # KV_MAX_LEAVES
+REUSE_COMPACT_STEP = 1  # KV_REUSE_COMPACT_STEP
 
 
 class SearchParams(C.Structure):
@@ -117,6 +119,8 @@ def _declare(L):
         "kv_records": ([vp, P(Record), sz, P(sz)], i),
         "kv_games": ([vp, P(Game), sz, P(sz)], i),
         "kv_stats_get": ([vp, P(Stats)], i),
+        "kv_sizeof_config": ([], sz),
+        "kv_sizeof_stats": ([], sz),
         "kv_root_visits": ([vp, P(C.c_int32), sz, P(sz)], i),
         "kv_root_visits_device": ([vp, vp, sz, P(sz), vp], i),
         "kv_root_moves": ([vp, P(C.c_uint16), sz, P(sz)], i),
@@ -180,7 +184,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_net_forward_boards", "kv_net_forward_boards_legal", "kv_net_set_timing", "kv_net_last_timing", "kv_net_destroy", "kv_net_set_precision", "kv_net_set_algo",
             "kv_net_calibration", "kv_engine_calibration",
             "kv_create",
-            "kv_load_weights", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
+            "kv_load_weights", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_sizeof_config", "kv_sizeof_stats", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
             "kv_search", "kv_sizeof_search_result", "kv_search_advance", "kv_search_continue", "kv_search_tree_size",
             "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm",
             "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_i8gemm_bench",
@@ -203,6 +207,9 @@ def lib():
         L = _declare(C.CDLL(LIB_PATH))
         if hasattr(L, "kv_sizeof_search_result"):  # EXPORTED (checked by build()) lists what must be there
             assert L.kv_sizeof_search_result() == C.sizeof(SearchResult), "kv_search_result: ctypes mirror differs"
+        if hasattr(L, "kv_sizeof_config"):  # (a library of before these exports reads a prefix of both mirrors)
+            assert L.kv_sizeof_config() == C.sizeof(Config), "kv_config: ctypes mirror differs"
+            assert L.kv_sizeof_stats() == C.sizeof(Stats), "kv_stats: ctypes mirror differs"
         _lib = L
     return _lib
 

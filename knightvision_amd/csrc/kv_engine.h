@@ -60,6 +60,8 @@ struct Ctr {
     int error;
     int need_eval;  // KV_EVAL_LAZY: some slot consumes a network row this step
     int comp_rows;  // KV_EVAL_LAZY above 16 slots: network rows of this step's compact batch
+    unsigned long long sims_kept;      // reuse_tree: root visits the committed plies' roots carried in
+    unsigned long long roots_carried;  // reuse_tree: committed plies whose root was a carried tree
 };
 
 struct DevCfg {
@@ -106,6 +108,9 @@ struct MctsSlot {  // per-slot search scratch (kv_mcts.hip)
     float root_value;
     int root_wtm;
     int overflow;      // expansions skipped because the slot's edge / node pool was full (an error)
+    // pad[0], pad[1]: network rows consumed / leaf rows sent this move (k_mcts_root). With reuse_tree
+    // (Tree::rem): pad[2] 1: the tree is a carried one (k_mcts_carry), pad[3] the root edge k_mcts_choose
+    // picked (-1 once k_mcts_carry has taken it), pad[4] the root visits this ply's root carried in
     int pad[5];
 };
 
@@ -135,6 +140,7 @@ struct Tree {  // per-slot SoA edge pools + node records, slot i at i*ecap / i*n
     int sims;
     uint16_t* e_V;  // position search with several leaves in flight (kv_search.hip): descents in flight per edge
     uint16_t* root_moves;  // optional [record_cap][MAXM]: the root's move words beside root_visits, 0xffff padded
+    int* rem;  // reuse_tree only (else NULL) [slot]: sim-steps the slot's next ply runs, sims - carried visits; 0: idle
 };
 
 // ---- position search (kv_search.hip): per-tree state, per-(tree, j) descents of the running sim-step ----
@@ -393,15 +399,18 @@ __device__ inline unsigned long long commit_move(const DevCfg& cfg, Slot& s, int
 // MCTS launches (kv_mcts.hip), all on `st`
 int mcts_root(const DevCfg& cfg, const Tree& t, Slot* slots, const uint16_t* moves, const float* logits,
               const float* values, float* probs_scratch, uint32_t* np_mt, Ctr* ctr, hipStream_t st);
-// select / backup for slots [slot0, slot0 + count)
+// select / backup for slots [slot0, slot0 + count); reuse: the kernels of kv_config.reuse_tree, in which a
+// slot whose root holds sims visits takes no descent and no backup
 int mcts_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, int8_t* nn_boards,
-                Ctr* ctr, hipStream_t st, int slot0, int count);
+                Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse = false);
 int mcts_backup(const DevCfg& cfg, const Tree& t, const Slot* slots, const float* logits, const float* values,
-                float* probs, Ctr* ctr, hipStream_t st, int slot0, int count);
+                float* probs, Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse = false);
 // backup of one sim-step fused with the next sim-step's select
 int mcts_backup_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, const float* logits,
                        const float* values, float* probs, int8_t* nn_boards, Ctr* ctr, hipStream_t st, int slot0,
-                       int count);
+                       int count, bool reuse = false);
+// reuse_tree: after k_finish, every slot's tree carried (re-rooted on the played edge's child) or dropped
+int mcts_carry(const DevCfg& cfg, const Tree& t, const Slot* slots, Ctr* ctr, hipStream_t st);
 int mcts_choose(const DevCfg& cfg, const Tree& t, Slot* slots, int8_t* boards, uint32_t* py_mt, kv_record* rec,
                 int8_t* last_board, Ctr* ctr, hipStream_t st);
 int hash_eval(const int8_t* boards, int rows, float* logits, float* values, hipStream_t st);

@@ -357,9 +357,11 @@ __global__ __launch_bounds__(1024) void k_compact(DevCfg cfg, const Slot* slots,
 // past the count (padding up to the > 16-board class) repeat row 0; row_of[i]
 // = the slot's row or -1. The network is batch-invariant bit for bit inside a
 // class, so every active slot's leaf row equals its row in the full batch and
-// the searches are unchanged (tests/test_mcts_gpu.py).
+// the searches are unchanged (tests/test_mcts_gpu.py). With kv_config.reuse_tree (node != NULL) the batch is
+// that of the slots still searching inside a ply: active and live, the root holding fewer than sims visits.
 __global__ __launch_bounds__(1024) void k_compact_active(DevCfg cfg, const Slot* slots, int rows, int* slot_of,
-                                                         int* row_of, Ctr* ctr) {
+                                                         int* row_of, Ctr* ctr, const NodeRec* node, int ncap,
+                                                         int sims) {
     __shared__ int wsum[16];
     __shared__ int base;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -367,7 +369,8 @@ __global__ __launch_bounds__(1024) void k_compact_active(DevCfg cfg, const Slot*
     __syncthreads();
     for (int c0 = 0; c0 < cfg.slots; c0 += 1024) {
         const int i = c0 + tid;
-        const bool act = i < cfg.slots && slots[i].status == ST_ACTIVE;
+        const bool act = i < cfg.slots && slots[i].status == ST_ACTIVE &&
+                         (node == nullptr || node[(size_t)i * ncap].N - 1 < sims);
         const unsigned long long bal = __ballot(act);
         if (lane == 0) wsum[w] = __popcll(bal);
         __syncthreads();
@@ -382,7 +385,7 @@ __global__ __launch_bounds__(1024) void k_compact_active(DevCfg cfg, const Slot*
         __syncthreads();
     }
     const int cnt = base < rows ? base : rows;
-    // more active slots than the host sized the batch for: some slot would search on stale leaf rows
+    // more active (and live) slots than the host sized the batch for: some slot would search on stale leaf rows
     if (tid == 0 && base > rows) atomicOr(&ctr->error, 16);
     __syncthreads();
     const int first = cnt > 0 ? slot_of[0] : 0;
@@ -470,6 +473,10 @@ struct kv_engine {
     float* mc_logits = nullptr;
     float* mc_values = nullptr;
     long long mc_rows = 0;  // leaf rows the compact batches sent through the network
+    long long full_rows = 0;  // leaf rows of the full-slot batches (kv_stats.leaf_batch_rows = mc_rows + full_rows)
+    // reuse_tree: tree.rem read back with the per-ply counters (pinned), and the slots per rem value
+    int* rem_host = nullptr;
+    std::vector<int> rem_hist;
     // kv_records_device / kv_root_visits_device copy out of e->rec / root_visits on the caller's
     // stream; the next write to those buffers (kv_run, kv_reset_records) or their release
     // (kv_destroy) waits for that copy on e->st
@@ -518,14 +525,19 @@ static int eng_counters(kv_engine* e, bool check_error = true) {
     hipLaunchKernelGGL(kv::k_count, dim3(1), dim3(256), 0, e->st, e->dc, e->slots, e->ctr);
     KV_HIP(hipGetLastError());
     KV_HIP(hipMemcpyAsync(e->ctr_host, e->ctr, sizeof(kv::Ctr), hipMemcpyDeviceToHost, e->st));
+    if (e->rem_host)  // reuse_tree: the sim-steps every slot's next ply runs
+        KV_HIP(hipMemcpyAsync(e->rem_host, e->tree.rem, (size_t)e->cfg.slots * sizeof(int), hipMemcpyDeviceToHost,
+                              e->st));
     KV_HIP(hipStreamSynchronize(e->st));
     if (check_error && e->ctr_host->error) {
         kv::set_error("engine device error flags 0x%x (1: move list overflow, 2: record buffer full, "
                       "4: MCTS tree pool full, %llu expansions dropped -- raise kv_config.tree_edge_cap; "
                       "8: move weights not finite -- every Dirichlet gamma draw of a ply was 0, where the "
                       "reference's random.choices raises ValueError; 16: more active MCTS slots than the compact "
-                      "leaf batch holds -- a host / device count mismatch)",
+                      "leaf batch holds -- a host / device count mismatch; 32: a carried tree and the position after "
+                      "the move disagree (reuse_tree))",
                       e->ctr_host->error, (unsigned long long)e->ctr_host->tree_overflows);
+        if (e->ctr_host->error & 32) return KV_EHIP;
         return (e->ctr_host->error & (8 | 16)) ? KV_EINVAL : KV_EOVERFLOW;
     }
     return KV_OK;
@@ -570,6 +582,11 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
                    (cfg->eval_mode == KV_EVAL_LAZY && cfg->sims == 0),
                KV_EINVAL, "kv_create: eval_mode %d not available (lazy: reference move selection only)",
                cfg->eval_mode);
+    KV_REQUIRE(cfg->reuse_tree == 0 || cfg->reuse_tree == 1, KV_EINVAL, "kv_create: reuse_tree %d must be 0 or 1",
+               cfg->reuse_tree);
+    KV_REQUIRE(cfg->reuse_tree == 0 || cfg->sims >= 1, KV_EINVAL,
+               "kv_create: reuse_tree carries MCTS subtrees and needs sims >= 1 (sims 0 is the reference move "
+               "selection)");
     KV_HIP(hipSetDevice(cfg->device));
     kv_engine* e = new kv_engine();
     e->cfg = *cfg;
@@ -660,6 +677,7 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
             ALLOC(e->mc_logits, S * kv::MAXM * sizeof(float));
             ALLOC(e->mc_values, S * sizeof(float));
         }
+        if (cfg->reuse_tree) ALLOC(t.rem, S * sizeof(int));
         t.ms = e->ms;
         std::vector<float> sq(t.ncap + 2);
         for (int k = 0; k < t.ncap + 2; ++k) sq[k] = (float)sqrt((double)k);
@@ -673,6 +691,12 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     }
 #undef ALLOC
     if (hipHostMalloc(&e->ctr_host, sizeof(kv::Ctr)) != hipSuccess) {
+        kv_destroy(e);
+        kv::set_error("kv_create: hipHostMalloc failed");
+        return KV_ENOMEM;
+    }
+    if (e->tree.rem && hipHostMalloc(&e->rem_host, S * sizeof(int)) != hipSuccess) {
+        e->rem_host = nullptr;
         kv_destroy(e);
         kv::set_error("kv_create: hipHostMalloc failed");
         return KV_ENOMEM;
@@ -697,6 +721,11 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     hipLaunchKernelGGL(kv::k_init, dim3((cfg->slots + 63) / 64), dim3(64), 0, e->st, d, e->slots, e->boards,
                        e->np_mt, e->py_mt, e->ctr);
     KV_HIP(hipGetLastError());
+    // reuse_tree: no slot holds a tree yet -- rem = sims for the slots k_init started, 0 for the idle ones
+    if (e->tree.rem && (rc = kv::mcts_carry(d, e->tree, e->slots, e->ctr, e->st))) {
+        kv_destroy(e);
+        return rc;
+    }
     KV_HIP(hipStreamSynchronize(e->st));
     *out = e;
     return KV_OK;
@@ -758,6 +787,70 @@ static int eng_eval(kv_engine* e, const int8_t* boards, int rows, bool leaf = fa
     return rc;
 }
 
+}  // extern "C"
+
+// One ply's root and sim-steps with kv_config.reuse_tree (DESIGN.md "Carried subtrees in self-play"). The host
+// read every slot's rem with the last counters (0 for a slot that was not active), so it knows for every
+// sim-step k the live count #{rem > k} and runs max rem steps. While every slot is live the full-slot batch
+// runs as without reuse; from the first step with a slot that is not, the leaf batch is the compact batch of
+// the active and live slots, rebuilt at every step whose live count is lower than at the last rebuild by at
+// least KV_REUSE_COMPACT_STEP. A slot that k_movegen finished this ply only makes the host's counts upper
+// bounds (padding rows); more live slots on the device than the batch holds raise error flag 16.
+static int eng_reuse_sims(kv_engine* e, int act) {
+    const kv::Tree& t = e->tree;
+    const int S = e->cfg.slots, sims = e->dc.sims;
+    int rc = KV_OK;
+    std::vector<int>& hist = e->rem_hist;  // hist[r]: slots whose ply runs r sim-steps
+    hist.assign((size_t)sims + 2, 0);
+    int steps = 0, counted = 0;
+    for (int i = 0; i < S; ++i) {
+        const int r = std::min(std::max(e->rem_host[i], 0), sims);
+        hist[r] += 1;
+        steps = std::max(steps, r);
+        counted += r > 0;
+    }
+    KV_REQUIRE(counted == act, KV_EHIP, "kv_run: %d active slots, %d with sim-steps to run (reuse_tree)", act,
+               counted);
+    if ((rc = kv::mcts_root(e->dc, t, e->slots, e->moves, e->logits, e->values, e->probs, e->np_mt, e->ctr, e->st)))
+        return rc;
+    if ((rc = kv::mcts_select(e->dc, t, e->slots, e->boards, e->nn_boards, e->ctr, e->st, 0, S, true))) return rc;
+    int live = act;      // slots with rem > k
+    int compacted = -1;  // the live count at the last compaction of this ply (-1: none yet)
+    int R = 0;
+    for (int k = 0; k < steps; ++k) {
+        if (k > 0) live -= hist[k];  // the slots whose last step was k - 1
+        const bool comp = e->mc_slot_of != nullptr && live < S;
+        if (comp) {
+            if (compacted < 0 || compacted - live >= KV_REUSE_COMPACT_STEP) {
+                R = S > 16 ? std::max(live, 17) : live;
+                hipLaunchKernelGGL(kv::k_compact_active, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, R,
+                                   e->mc_slot_of, e->mc_row_of, e->ctr, (const kv::NodeRec*)t.node, t.ncap, sims);
+                KV_HIP(hipGetLastError());
+                compacted = live;
+            }
+            hipLaunchKernelGGL(kv::k_gather_leaves, dim3(R), dim3(64), 0, e->st, e->mc_slot_of, e->nn_boards,
+                               t.leaf_moves, t.leaf_cnt, e->mc_boards, e->mc_moves, e->mc_cnt);
+            KV_HIP(hipGetLastError());
+            if ((rc = eng_eval(e, e->mc_boards, R, true, true))) return rc;
+            hipLaunchKernelGGL(kv::k_scatter_leaves, dim3(R), dim3(64), 0, e->st, e->mc_slot_of, e->mc_row_of,
+                               e->mc_logits, e->mc_values, e->mc_cnt, t.leaf_logits, e->values);
+            KV_HIP(hipGetLastError());
+            e->mc_rows += R;
+        } else {
+            if ((rc = eng_eval(e, e->nn_boards, S, true))) return rc;
+            e->full_rows += S;
+        }
+        rc = k + 1 < steps ? kv::mcts_backup_select(e->dc, t, e->slots, e->boards, e->logits, e->values, e->probs,
+                                                    e->nn_boards, e->ctr, e->st, 0, S, true)
+                           : kv::mcts_backup(e->dc, t, e->slots, e->logits, e->values, e->probs, e->ctr, e->st, 0, S,
+                                             true);
+        if (rc) return rc;
+    }
+    return KV_OK;
+}
+
+extern "C" {
+
 int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
     KV_REQUIRE(e && e->loaded, KV_EINVAL, "kv_run: engine has no weights");
     KV_REQUIRE(e->used != 2, KV_EINVAL,
@@ -813,35 +906,41 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
             // fewer active slots than slots (no game left to start): compact leaf batches of the active
             // slots, padded to the network class of the full batch (> 16 boards: at least 17 rows)
             const int act = e->ctr_host->active;
-            const bool comp = e->mc_slot_of != nullptr && act < S;
-            const int R = comp ? (S > 16 ? std::max(act, 17) : act) : S;
-            if (comp) {
-                hipLaunchKernelGGL(kv::k_compact_active, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, R,
-                                   e->mc_slot_of, e->mc_row_of, e->ctr);
-                KV_HIP(hipGetLastError());
-            }
-            if ((rc = kv::mcts_root(e->dc, t, e->slots, e->moves, e->logits, e->values, e->probs, e->np_mt, e->ctr, e->st)))
-                return rc;
-            if ((rc = kv::mcts_select(e->dc, t, e->slots, e->boards, e->nn_boards, e->ctr, e->st, 0, S))) return rc;
-            for (int k = 0; k < e->dc.sims; ++k) {
+            if (e->tree.rem) {
+                if ((rc = eng_reuse_sims(e, act))) return rc;
+            } else {
+                const bool comp = e->mc_slot_of != nullptr && act < S;
+                const int R = comp ? (S > 16 ? std::max(act, 17) : act) : S;
                 if (comp) {
-                    hipLaunchKernelGGL(kv::k_gather_leaves, dim3(R), dim3(64), 0, e->st, e->mc_slot_of, e->nn_boards,
-                                       t.leaf_moves, t.leaf_cnt, e->mc_boards, e->mc_moves, e->mc_cnt);
+                    hipLaunchKernelGGL(kv::k_compact_active, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, R,
+                                       e->mc_slot_of, e->mc_row_of, e->ctr, (const kv::NodeRec*)nullptr, 0, 0);
                     KV_HIP(hipGetLastError());
-                    if ((rc = eng_eval(e, e->mc_boards, R, true, true))) return rc;
-                    hipLaunchKernelGGL(kv::k_scatter_leaves, dim3(R), dim3(64), 0, e->st, e->mc_slot_of,
-                                       e->mc_row_of, e->mc_logits, e->mc_values, e->mc_cnt, t.leaf_logits,
-                                       e->values);
-                    KV_HIP(hipGetLastError());
-                    e->mc_rows += R;
-                } else if ((rc = eng_eval(e, e->nn_boards, S, true))) {
-                    return rc;
                 }
-                rc = k + 1 < e->dc.sims
-                         ? kv::mcts_backup_select(e->dc, t, e->slots, e->boards, e->logits, e->values, e->probs,
-                                                  e->nn_boards, e->ctr, e->st, 0, S)
-                         : kv::mcts_backup(e->dc, t, e->slots, e->logits, e->values, e->probs, e->ctr, e->st, 0, S);
-                if (rc) return rc;
+                if ((rc = kv::mcts_root(e->dc, t, e->slots, e->moves, e->logits, e->values, e->probs, e->np_mt, e->ctr, e->st)))
+                    return rc;
+                if ((rc = kv::mcts_select(e->dc, t, e->slots, e->boards, e->nn_boards, e->ctr, e->st, 0, S))) return rc;
+                for (int k = 0; k < e->dc.sims; ++k) {
+                    if (comp) {
+                        hipLaunchKernelGGL(kv::k_gather_leaves, dim3(R), dim3(64), 0, e->st, e->mc_slot_of, e->nn_boards,
+                                           t.leaf_moves, t.leaf_cnt, e->mc_boards, e->mc_moves, e->mc_cnt);
+                        KV_HIP(hipGetLastError());
+                        if ((rc = eng_eval(e, e->mc_boards, R, true, true))) return rc;
+                        hipLaunchKernelGGL(kv::k_scatter_leaves, dim3(R), dim3(64), 0, e->st, e->mc_slot_of,
+                                           e->mc_row_of, e->mc_logits, e->mc_values, e->mc_cnt, t.leaf_logits,
+                                           e->values);
+                        KV_HIP(hipGetLastError());
+                        e->mc_rows += R;
+                    } else if ((rc = eng_eval(e, e->nn_boards, S, true))) {
+                        return rc;
+                    } else {
+                        e->full_rows += S;
+                    }
+                    rc = k + 1 < e->dc.sims
+                             ? kv::mcts_backup_select(e->dc, t, e->slots, e->boards, e->logits, e->values, e->probs,
+                                                      e->nn_boards, e->ctr, e->st, 0, S)
+                             : kv::mcts_backup(e->dc, t, e->slots, e->logits, e->values, e->probs, e->ctr, e->st, 0, S);
+                    if (rc) return rc;
+                }
             }
             if ((rc = kv::mcts_choose(e->dc, t, e->slots, e->boards, e->py_mt, e->rec, e->last_board, e->ctr,
                                       e->st)))
@@ -850,6 +949,7 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
         hipLaunchKernelGGL(kv::k_finish, dim3(S), dim3(128), 0, e->st, e->dc, e->slots, e->boards,
                            e->moves, e->np_mt, e->py_mt, e->games, e->ctr);
         KV_HIP(hipGetLastError());
+        if (e->tree.rem && (rc = kv::mcts_carry(e->dc, e->tree, e->slots, e->ctr, e->st))) return rc;
         ++done;
         ++e->steps;
         if (done % check_every == 0 || (max_steps >= 0 && done >= max_steps)) {
@@ -1255,8 +1355,14 @@ int kv_stats_get(kv_engine* e, kv_stats* out) {
     snprintf(out->dom_kernel, sizeof(out->dom_kernel), "%s", e->dom_kernel ? e->dom_kernel : "");
     out->tree_overflows = (int64_t)e->ctr_host->tree_overflows;
     out->nn_rows_lazy = e->lazy_rows;
+    out->sims_kept = (int64_t)e->ctr_host->sims_kept;
+    out->roots_carried = (int64_t)e->ctr_host->roots_carried;
+    out->leaf_batch_rows = e->mc_rows + e->full_rows;
     return KV_OK;
 }
+
+size_t kv_sizeof_config(void) { return sizeof(kv_config); }
+size_t kv_sizeof_stats(void) { return sizeof(kv_stats); }
 
 int kv_root_visits(kv_engine* e, int32_t* out, size_t cap, size_t* n) {
     KV_REQUIRE(e && n, KV_EINVAL, "kv_root_visits: NULL argument");
@@ -1350,11 +1456,12 @@ void kv_destroy(kv_engine* e) {
                     e->mc_logits, e->mc_values,
                     t.e_V, e->sw.ss, e->sw.lf, e->sw.paths, e->sw.lboards, e->sw.lmoves, e->sw.lcnt, e->sw.llogits,
                     e->sw.lvalues, e->sw.remaining, e->sw.res, e->s_states, e->s_rboards, e->s_rlogits,
-                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves};
+                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves, t.rem};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (e->ctr_host) (void)hipHostFree(e->ctr_host);
     if (e->s_rem_host) (void)hipHostFree(e->s_rem_host);
+    if (e->rem_host) (void)hipHostFree(e->rem_host);
     for (auto x : e->ev) (void)hipEventDestroy(x);
     if (e->copy_done) (void)hipEventDestroy(e->copy_done);
     if (e->net) kv_net_destroy(e->net);

@@ -24,6 +24,9 @@
 //            caller shrinks it) raises KV_EOVERFLOW.
 //   choose : random.choices over the root visit counts on the CPython stream
 //            (tau = 1), then makeMove / record / termination as the reference.
+// With kv_config.reuse_tree the subtree under the move just played is carried into the next ply
+// (k_mcts_carry, DESIGN.md "Carried subtrees in self-play"): the root takes the fresh root's mixed priors, N,
+// W and the children below it stay, and a slot searches only while its root holds fewer than sims visits.
 // Tree: structure-of-arrays edge pools per slot in HBM (move u16, P f32, N u16,
 // W f32, child u16 per edge: 14 B; a node's edges start on a 16-edge boundary)
 // and one 16-byte record per node (first edge, edge count; N for the root only:
@@ -32,6 +35,7 @@
 #include <math.h>
 
 #include "kv_engine.h"
+#include "kv_tree_pack.h"
 
 #pragma clang fp contract(off)
 
@@ -66,6 +70,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         return;
     }
     const size_t eb = (size_t)i * t.ecap, nb = (size_t)i * t.ncap;
+    if (t.rem != nullptr && t.ms[i].pad[2] != 0) {
+        // a carried tree (k_mcts_carry): node 0 keeps its visits, values and children and takes only the
+        // priors a fresh root would get; the regenerated move list must be node 0's move words
+        const NodeRec r0 = t.node[nb];
+        bool bad = r0.cnt != n || r0.first != 0;
+        for (int j = lane; j < n && j < r0.cnt; j += 256) bad = bad || t.e_move[eb + j] != ml[j];
+        if (__syncthreads_or(bad)) {
+            if (lane == 0) {
+                atomicOr(&ctr->error, 32);
+                t.node[nb].N = t.sims + 1;  // never searched on: the slot is not live in any sim-step
+            }
+            return;
+        }
+        for (int j = lane; j < n; j += 256)
+            t.e_P[eb + j] = total == 0.0 ? 1.0f / (float)n : (float)(vals[j] / total);
+        if (lane == 0) {
+            MctsSlot m = t.ms[i];
+            m.root_value = values[i];
+            m.path_len = 0;
+            m.leaf_pending = 0;
+            m.pad[0] = 1;
+            m.pad[1] = 0;
+            m.pad[4] = r0.N - 1;  // the visits carried in: they count toward sims
+            t.ms[i] = m;
+            slots[i].last_value = values[i];
+        }
+        return;
+    }
     for (int j = lane; j < n; j += 256) {
         t.e_move[eb + j] = ml[j];
         t.e_P[eb + j] = total == 0.0 ? 1.0f / (float)n : (float)(vals[j] / total);
@@ -84,19 +116,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         m.leaf_pending = 0;
         m.pad[0] = 1;  // network rows consumed this move
         m.pad[1] = 0;  // leaf rows sent to the network this move (Ctr::nn_rows at the choice)
+        m.pad[4] = 0;
         t.ms[i] = m;
         slots[i].last_value = values[i];
     }
 }
 
-// one slot's select, by the 64 threads of its workgroup
+// one slot's select, by the 64 threads of its workgroup. REUSE (kv_config.reuse_tree): a slot whose root
+// already holds sims visits (carried ones counting) is not live: no descent, no leaf
+template <bool REUSE>
 __device__ inline void mcts_select_slot(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards,
                                         int8_t* nn_boards, Ctr* ctr, int i) {
     __shared__ int8_t bd[64];
     __shared__ int s_meta[8];  // wtm wkr wkc bkr bkc flags ep
     const int lane = threadIdx.x;
     const Slot s = slots[i];
-    if (s.status != ST_ACTIVE) {
+    if (s.status != ST_ACTIVE || (REUSE && t.node[(size_t)i * t.ncap].N - 1 >= t.sims)) {
         if (lane == 0) t.leaf_cnt[i] = 0;  // no logits for this row of the batch
         return;
     }
@@ -174,13 +209,16 @@ __device__ inline void mcts_select_slot(const DevCfg& cfg, const Tree& t, const 
     nn_boards[(size_t)i * 64 + lane] = bd[lane];
 }
 
-// one slot's backup, by the 64 threads of its workgroup
+// one slot's backup, by the 64 threads of its workgroup (REUSE: a no-op for a slot that was not live in the
+// step's select -- its root count has not changed since)
+template <bool REUSE>
 __device__ inline void mcts_backup_slot(const DevCfg& cfg, const Tree& t, const Slot* slots, const float* logits,
                                         const float* values, float* probs, Ctr* ctr, int i) {
     __shared__ float pri[MAXM];
     const int lane = threadIdx.x;
     const Slot s = slots[i];
     if (s.status != ST_ACTIVE) return;
+    if (REUSE && t.node[(size_t)i * t.ncap].N - 1 >= t.sims) return;
     MctsSlot m = t.ms[i];
     const size_t eb = (size_t)i * t.ecap, nb = (size_t)i * t.ncap;
     float v = m.leaf_value;
@@ -254,28 +292,31 @@ __device__ inline void mcts_backup_slot(const DevCfg& cfg, const Tree& t, const 
     }
 }
 
+template <bool REUSE>
 __global__ __launch_bounds__(64) void k_mcts_select(DevCfg cfg, Tree t, const Slot* slots, const int8_t* boards,
                                                     int8_t* nn_boards, Ctr* ctr, int slot0) {
-    mcts_select_slot(cfg, t, slots, boards, nn_boards, ctr, slot0 + blockIdx.x);
+    mcts_select_slot<REUSE>(cfg, t, slots, boards, nn_boards, ctr, slot0 + blockIdx.x);
 }
 
+template <bool REUSE>
 __global__ __launch_bounds__(64) void k_mcts_backup(DevCfg cfg, Tree t, const Slot* slots, const float* logits,
                                                     const float* values, float* probs, Ctr* ctr, int slot0) {
-    mcts_backup_slot(cfg, t, slots, logits, values, probs, ctr, slot0 + blockIdx.x);
+    mcts_backup_slot<REUSE>(cfg, t, slots, logits, values, probs, ctr, slot0 + blockIdx.x);
 }
 
 // backup of sim-step k and select of sim-step k+1 for the same slot in one
 // launch (a slot's next descent depends only on its own tree): one kernel
 // boundary less per sim-step. The barrier orders thread 0's tree writes
 // before the descent reads them (workgroup scope).
+template <bool REUSE>
 __global__ __launch_bounds__(64) void k_mcts_backup_select(DevCfg cfg, Tree t, const Slot* slots,
                                                            const int8_t* boards, const float* logits,
                                                            const float* values, float* probs, int8_t* nn_boards,
                                                            Ctr* ctr, int slot0) {
     const int i = slot0 + blockIdx.x;
-    mcts_backup_slot(cfg, t, slots, logits, values, probs, ctr, i);
+    mcts_backup_slot<REUSE>(cfg, t, slots, logits, values, probs, ctr, i);
     __syncthreads();
-    mcts_select_slot(cfg, t, slots, boards, nn_boards, ctr, i);
+    mcts_select_slot<REUSE>(cfg, t, slots, boards, nn_boards, ctr, i);
 }
 
 __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* slots, int8_t* boards,
@@ -296,8 +337,18 @@ __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* sl
     // the move's counters in one update per slot (one device-scope atomic per
     // slot and sim-step on a shared counter cost ~3.5 us per select / backup)
     if (lane == 0) {
-        atomicAdd(&ctr->sims, (unsigned long long)cfg.sims);
+        // reuse_tree: the ply's new backups; the visits its root carried in are counted beside them, at the
+        // choice like sims, so that sims + sims_kept == plies x cfg.sims whenever kv_run returns
+        const int kept = t.rem != nullptr ? m.pad[4] : 0;
+        atomicAdd(&ctr->sims, (unsigned long long)(cfg.sims - kept));
         atomicAdd(&ctr->nn_rows, (unsigned long long)m.pad[1]);
+        if (t.rem != nullptr) {
+            t.ms[i].pad[3] = s_pick;  // the played root edge, for k_mcts_carry
+            if (m.pad[2] != 0) {
+                atomicAdd(&ctr->sims_kept, (unsigned long long)kept);
+                atomicAdd(&ctr->roots_carried, 1ull);
+            }
+        }
     }
     s.last_value = m.root_value;  // resign test on the root's network value (:185)
     s.n_evals += m.pad[0];
@@ -311,6 +362,49 @@ __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* sl
         }
     }
     if (lane == 0) slots[i] = s;
+}
+
+// kv_config.reuse_tree, once per ply after k_finish: a slot whose game goes on after the move at root edge k
+// keeps the subtree of that edge's child as its tree (tree_pack_subtree, a session's re-root); without a
+// child, or when the game ended, a recycled slot started a new game or the slot is idle, the tree is dropped
+// and the next ply builds a fresh root. rem[i] = the sim-steps the slot's next ply runs (0: not active).
+// One wavefront per slot.
+__global__ __launch_bounds__(64) void k_mcts_carry(DevCfg cfg, Tree t, const Slot* slots, Ctr* ctr) {
+    __shared__ uint32_t keep[KEEP_WORDS];
+    __shared__ int below[KEEP_WORDS];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const Slot s = slots[i];
+    MctsSlot m = t.ms[i];
+    const size_t eb = (size_t)i * t.ecap, nb = (size_t)i * t.ncap;
+    const int k = m.pad[3];
+    // the game goes on: still active after k_finish with a move committed (a recycled slot is at ply 0), the
+    // move being the one k_mcts_choose picked this ply
+    const bool goes_on = s.status == ST_ACTIVE && s.ply > 0 && k >= 0 && m.node_count >= 1 && k < t.node[nb].cnt;
+    int c = NO_CHILD, played_n = 0;
+    if (goes_on) {
+        c = t.e_child[eb + k];
+        played_n = t.e_N[eb + k];
+    }
+    bool carried = c != NO_CHILD;
+    if (carried && (c <= 0 || c >= m.node_count || played_n < 1 || played_n > t.sims)) {
+        if (lane == 0) atomicOr(&ctr->error, 32);  // not a tree this search built: dropped
+        carried = false;
+    }
+    PackedTree pk = {0, 0, 0, 0.f};
+    if (carried) {
+        pk = tree_pack_subtree(t, eb, nb, c, m.node_count, played_n, keep, below);
+        if (pk.moved != pk.nodes && lane == 0) atomicOr(&ctr->error, 32);
+    }
+    if (lane != 0) return;
+    m.pad[2] = carried ? 1 : 0;
+    m.pad[3] = -1;
+    if (carried) {
+        m.node_count = pk.nodes;
+        m.edge_count = pk.edges;
+        m.root_wtm = s.wtm;  // the side to move after the committed move: the old root's, flipped
+    }
+    t.ms[i] = m;
+    t.rem[i] = s.status != ST_ACTIVE ? 0 : carried ? t.sims - (played_n - 1) : t.sims;
 }
 
 // Test evaluator (KV_EVAL_HASH): all logits 0 (uniform priors, exact in
@@ -351,25 +445,38 @@ int mcts_root(const DevCfg& cfg, const Tree& t, Slot* slots, const uint16_t* mov
 }
 
 int mcts_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, int8_t* nn_boards,
-                Ctr* ctr, hipStream_t st, int slot0, int count) {
-    hipLaunchKernelGGL(k_mcts_select, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, nn_boards, ctr, slot0);
+                Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse) {
+    if (reuse)
+        hipLaunchKernelGGL(k_mcts_select<true>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, nn_boards, ctr,
+                           slot0);
+    else
+        hipLaunchKernelGGL(k_mcts_select<false>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, nn_boards, ctr,
+                           slot0);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
 
 int mcts_backup(const DevCfg& cfg, const Tree& t, const Slot* slots, const float* logits, const float* values,
-                float* probs, Ctr* ctr, hipStream_t st, int slot0, int count) {
-    hipLaunchKernelGGL(k_mcts_backup, dim3(count), dim3(64), 0, st, cfg, t, slots, logits, values, probs, ctr,
-                       slot0);
+                float* probs, Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse) {
+    if (reuse)
+        hipLaunchKernelGGL(k_mcts_backup<true>, dim3(count), dim3(64), 0, st, cfg, t, slots, logits, values, probs,
+                           ctr, slot0);
+    else
+        hipLaunchKernelGGL(k_mcts_backup<false>, dim3(count), dim3(64), 0, st, cfg, t, slots, logits, values, probs,
+                           ctr, slot0);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
 
 int mcts_backup_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, const float* logits,
                        const float* values, float* probs, int8_t* nn_boards, Ctr* ctr, hipStream_t st, int slot0,
-                       int count) {
-    hipLaunchKernelGGL(k_mcts_backup_select, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, logits, values, probs,
-                       nn_boards, ctr, slot0);
+                       int count, bool reuse) {
+    if (reuse)
+        hipLaunchKernelGGL(k_mcts_backup_select<true>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, logits,
+                           values, probs, nn_boards, ctr, slot0);
+    else
+        hipLaunchKernelGGL(k_mcts_backup_select<false>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, logits,
+                           values, probs, nn_boards, ctr, slot0);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
@@ -378,6 +485,12 @@ int mcts_choose(const DevCfg& cfg, const Tree& t, Slot* slots, int8_t* boards, u
                 int8_t* last_board, Ctr* ctr, hipStream_t st) {
     hipLaunchKernelGGL(k_mcts_choose, dim3(cfg.slots), dim3(64), 0, st, cfg, t, slots, boards, py_mt, rec,
                        last_board, ctr);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
+}
+
+int mcts_carry(const DevCfg& cfg, const Tree& t, const Slot* slots, Ctr* ctr, hipStream_t st) {
+    hipLaunchKernelGGL(k_mcts_carry, dim3(cfg.slots), dim3(64), 0, st, cfg, t, slots, ctr);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }

@@ -38,7 +38,9 @@ class SelfPlayEngine:
     def __init__(self, weights, *, slots=256, n_games=256, seed=42, seed_mode=SEED_PER_GAME, max_moves=None,
                  batch=16, eps=0.25, alpha=0.3, sims=0, c_puct=1.5, eval_mode=EVAL_FAITHFUL, record_cap=None,
                  recycle=True, device=0, game_id_base=0, game_id_stride=1, precision="fp32",
-                 algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False):
+                 algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False, reuse_tree=False):
+        """reuse_tree (MCTS, sims >= 1): carry the subtree under the move just played into the next ply
+        (kv_config.reuse_tree); stats() then reports sims_kept / roots_carried."""
         L = _lib.lib()
         keep = 2 if keep_root_moves else (1 if keep_root_visits else 0)  # the move words imply the visits
         if record_cap is None:
@@ -53,7 +55,7 @@ class SelfPlayEngine:
                           max_moves=max_moves if max_moves else 0, batch=batch, eps=eps, alpha=alpha, sims=sims,
                           c_puct=c_puct, eval_mode=eval_mode, record_cap=record_cap, recycle=1 if recycle else 0,
                           precision=PRECISIONS[precision], algo=ALGOS[algo],
-                          tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep)
+                          tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep, reuse_tree=int(reuse_tree))
         h = C.c_void_p()
         _lib.check(L.kv_create(C.byref(cfg), C.byref(h)), "kv_create")
         self.h = h

@@ -67,12 +67,14 @@ def _dist():
 
 
 def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_moves=None, slots=256,
-                   precision="fp32", policy_targets=False):
+                   precision="fp32", policy_targets=False, reuse_tree=False):
     """This rank's share of one iteration's games, played by the HIP engine with
     the model's current weights. Returns (records, games) numpy arrays; with
     policy_targets (MCTS runs) also the root visit counts and root move words of
     every record, (records, games, visits uint16 [n, MAXM], moves uint16
-    [n, MAXM]) row for row, 0xffff past each position's move list."""
+    [n, MAXM]) row for row, 0xffff past each position's move list. reuse_tree (sims > 0): the engine carries
+    the subtree under each move played into the next ply (kv_config.reuse_tree); every root still holds sims
+    visits, so the visit targets are built as without it."""
     dist, rank, world = _dist()
     dev = torch.device(device)
     ids = list(range(rank, n_games, world))
@@ -86,7 +88,7 @@ def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_m
                         max_moves=max_moves, batch=SELFPLAY_BATCH, eps=EPSILON, alpha=ALPHA, sims=sims,
                         game_id_base=base, game_id_stride=world, device=dev.index or 0,
                         precision=precision, eval_mode=batched_eval_mode() if sims == 0 else 0,
-                        keep_root_moves=bool(policy_targets)) as eng:
+                        keep_root_moves=bool(policy_targets), reuse_tree=bool(reuse_tree)) as eng:
         eng.run()
         selfplay_shard.last_calibration = eng.calibration()  # the conv paths these weights ran on
         selfplay_shard.last_stats = eng.stats()
@@ -255,7 +257,7 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
                        batch_size: int = LEARN_BATCH_SIZE, lr: float = LEARN_LR,
                        accumulate_steps: int = T.ACCUM_STEPS, sims: int = 0, max_moves=None, slots: int = 256,
                        seed: int = 0, games_path: str | None = None, max_samples: int = 10000, log=print,
-                       policy_target: str = "move"):
+                       policy_target: str = "move", reuse_tree: bool = False):
     """Run the loop (learn.py reinforcement_loop :152-209); returns per-iteration statistics.
     `model` is a knightvision_amd.model.ChessNet (same parameters as ai/model.py) on `device`.
     `games_path`: the reference's JSONL dataset (ChessPGNDataset, :162) the self-play records extend --
@@ -264,7 +266,9 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
     `policy_target`: "move" (the reference's loss: cross-entropy against the move played) or "visits"
     (no reference counterpart): the policy trains on each self-play record's MCTS root visit distribution
     (soft cross-entropy, PolicyTargets + train_ops.policy_loss), which needs sims > 0; the samples of
-    `games_path` then carry their one-hot rows."""
+    `games_path` then carry their one-hot rows.
+    `reuse_tree` (sims > 0): self-play carries the searched subtree from ply to ply (kv_config.reuse_tree); the
+    per-iteration statistics then show the carried root visits (sims_kept) beside the new backups (sims)."""
     if policy_target not in ("move", "visits"):
         raise ValueError(f"reinforcement_loop: policy_target {policy_target!r}: 'move' or 'visits'")
     visits = policy_target == "visits"
@@ -302,10 +306,11 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
         pi = None
         if visits:
             recs, games, *pi = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves,
-                                              slots=slots, policy_targets=True)
+                                              slots=slots, policy_targets=True, reuse_tree=reuse_tree)
             pi = None if recs is None else tuple(pi)
         else:
-            recs, games = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves, slots=slots)
+            recs, games = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves, slots=slots,
+                                         reuse_tree=reuse_tree)
         st["selfplay_s"] = time.perf_counter() - t0
         cal = getattr(selfplay_shard, "last_calibration", None)
         if cal is not None:  # fp32 AUTO: the self-play network's conv path for this iteration's weights
@@ -315,7 +320,8 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
                 st["calib_err"] = {k: (cal["err_logit"][k], cal["err_value"][k]) for k in cal["err_logit"]}
         es = getattr(selfplay_shard, "last_stats", None)
         if es is not None:  # this rank's engine: plies and MCTS simulations (the throughput a path flip moves)
-            st.update(plies=int(es["plies"]), sims=int(es["sims"]))
+            st.update(plies=int(es["plies"]), sims=int(es["sims"]), sims_kept=int(es["sims_kept"]),
+                      leaf_batch_rows=int(es["leaf_batch_rows"]))
         model.train()
         data = extend_dataset(data, recs, games, dev, pi=pi, policy_targets=True) if visits \
             else extend_dataset(data, recs, games, dev)

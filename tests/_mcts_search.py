@@ -1,12 +1,19 @@
 """Plain-Python restatement of the position search (DESIGN.md "MCTS semantics",
-knightvision_amd/csrc/kv_search.hip) over the oracle's rules, for the hash test
-evaluator: all logits 0, so the leaf priors are exactly 1/n and the root's
-(eps = 0) the float of the double 1/n; the value of a position is the FNV-1a
-hash of the 64 board codes after getValidMoves, as k_hash_eval computes it.
-Every score is built from numpy float32 scalars in the kernel's operation
-order, so visit counts, q and the principal variation must equal the
-device's bit for bit. Shared by tests/test_mcts_search_cpu.py and
-tests/test_mcts_search_gpu.py; not a test module itself."""
+knightvision_amd/csrc/kv_search.hip) over the oracle's rules, for any
+evaluator: evaluate(list of states after getValidMoves) -> [(logits[4096],
+value)], one call for the root and one per sim-step for the step's pending
+leaves in descent order, as the device batches them. The root's priors are
+k_mcts_root's (root_priors: the softmax over the 4,096 logits, restricted to
+the legal moves, mixed with the Dirichlet noise of the position's own stream
+and renormalised in double), an expanded leaf's are the backup's (leaf_priors:
+the softmax over the legal logits only). Without an evaluator it is the hash
+test evaluator: all logits 0, so the leaf priors are exactly 1/n and the
+root's (eps = 0) the float of the double 1/n; the value of a position is the
+FNV-1a hash of the 64 board codes after getValidMoves, as k_hash_eval computes
+it. Every score is built from numpy float32 scalars in the kernel's operation
+order, so visit counts, q, priors and the principal variation must equal the
+device's bit for bit. Shared by the test_mcts_search_* / test_mcts_session_*
+modules and tests/_mcts_selfplay_reuse.py; not a test module itself."""
 import functools
 
 import numpy as np
@@ -24,6 +31,102 @@ def hash_value(codes) -> np.float32:
         h ^= int(q) & 0xFF
         h = (h * 16777619) & 0xFFFFFFFF
     return F(F((h % 129) - 64) / F(64.0))
+
+
+def hash_eval(states):
+    """KV_EVAL_HASH's rows of positions (after getValidMoves): all logits 0, the board's hash value."""
+    return [(np.zeros(4096, dtype=F), hash_value(st[:64])) for st in states]
+
+
+def synthetic_logits(codes):
+    """4,096 non-uniform logits of a 64-code board: multiples of 1/8 in [-4, 4), the level of logit i taken
+    from a multiplicative mix of the board's FNV-1a hash and i. Dyadic, so every difference of two is exact."""
+    h = 2166136261
+    for q in codes:
+        h ^= int(q) & 0xFF
+        h = (h * 16777619) & 0xFFFFFFFF
+    x = (np.arange(4096, dtype=np.uint64) * np.uint64(2654435761) + np.uint64(h)) & np.uint64(0xFFFFFFFF)
+    x ^= x >> np.uint64(15)
+    x = (x * np.uint64(2246822519)) & np.uint64(0xFFFFFFFF)
+    x ^= x >> np.uint64(13)
+    return ((x & np.uint64(63)).astype(F) / F(8.0) - F(4.0)).astype(F)
+
+
+def synthetic_eval(state):
+    """A deterministic evaluator of one position (after getValidMoves) for the CPU tests: synthetic_logits
+    and the board's hash value."""
+    return synthetic_logits(state[:64]), hash_value(state[:64])
+
+
+def synthetic_eval_many(states):
+    """synthetic_eval as search()'s evaluate."""
+    return [synthetic_eval(st) for st in states]
+
+
+def synthetic_eval_planes(planes):
+    """synthetic_eval as oracle.mcts_play_game's eval_fn: planes[n, 12, 8, 8] -> logits[n, 4096], values[n]."""
+    planes = np.asarray(planes, dtype=F).reshape(-1, 12, 64)
+    codes = np.zeros((planes.shape[0], 64), dtype=np.int8)
+    b, c, s = np.nonzero(planes)
+    codes[b, s] = c + 1
+    rows = [synthetic_eval(cd) for cd in codes]
+    return np.stack([lg for lg, _ in rows]), np.array([v for _, v in rows], dtype=F)
+
+
+def rotated(evaluate):
+    """The evaluator that hands every row of a call its neighbour's logits (row k gets row k + 1's, the last
+    the first's) and keeps the values: what a search that pairs a step's leaves with the wrong logits rows
+    computes. The inputs of the multi-leaf tests must tell it from `evaluate`."""
+    def ev(states):
+        rows = evaluate(states)
+        return [(rows[(k + 1) % len(rows)][0], rows[k][1]) for k in range(len(rows))]
+    return ev
+
+
+def policy_index(word):
+    return (word & 63) * 64 + ((word >> 6) & 63)
+
+
+def root_priors(logits, words, np_mt, eps, alpha):
+    """k_mcts_root: softmax with det_expf over the 4,096 logits, the reference's mixed legal weights
+    (fp32 keep x p + fp64 eps x Dirichlet), normalised by their serial sum, one rounding to float."""
+    probs = O.softmax_det_4096(logits)
+    noise, _ = np_mt.dirichlet(alpha, 4096)
+    keep = F(1.0 - eps)
+    w = []
+    for wd in words:
+        idx = policy_index(wd)
+        w.append(np.float64(F(keep * probs[idx])) + np.float64(eps) * noise[idx])
+    total = np.float64(0.0)
+    for x in w:
+        total = total + x
+    n = len(words)
+    if total == 0.0:
+        return [F(1.0) / F(n)] * n
+    return [F(x / total) for x in w]
+
+
+def leaf_priors(logits, words):
+    """mcts_backup_slot: softmax over the legal moves' logits only; lane l sums entries l, l + 64, ... in
+    order, then the xor butterfly over the 64 lanes."""
+    lg = np.array([logits[policy_index(wd)] for wd in words], dtype=F)
+    n = len(lg)
+    mx = lg.max()
+    e = np.array([O.det_expf(float(F(x - mx))) for x in lg], dtype=F)
+    part = np.zeros(64, dtype=F)
+    for lane in range(64):
+        s = F(0.0)
+        for j in range(lane, n, 64):
+            s = F(s + e[j])
+        part[lane] = s
+    m = 32
+    while m >= 1:
+        part = (part + part[np.arange(64) ^ m]).astype(F)
+        m >>= 1
+    total = part[0]
+    if total > 0:
+        return (e / total).astype(F)
+    return np.full(n, F(1.0) / F(n), dtype=F)
 
 
 def move_words(state, moves3):
@@ -65,11 +168,12 @@ KINGS_ONLY_ROOT = make_state({sq("e1"): 1, sq("e8"): 7}, True)
 class _Node:
     __slots__ = ("state", "words", "P", "N", "V", "W", "child", "cstate")
 
-    def __init__(self, state, words, prior):
+    def __init__(self, state, words, priors):
         n = len(words)
         self.state = state  # after getValidMoves
         self.words = words
-        self.P = [prior] * n
+        self.P = [F(p) for p in priors]
+        assert len(self.P) == n
         self.N = [0] * n
         self.V = [0] * n
         self.W = [F(0.0)] * n
@@ -77,13 +181,38 @@ class _Node:
         self.cstate = [None] * n
 
 
-def search(state, sims, leaves=1, c_puct=1.5, ncap=None):
-    """-> dict(status, visits, q, prior, moves, best, pv, steps, nn_rows, root_value, accepted: the descents
-    each sim-step accepted)."""
+def fresh_root_row(evaluate, st, words, eps=0.0, alpha=0.3, seed=0):
+    """(priors, value) of a root built from nothing (k_mcts_root on the position's network row; seed: the
+    position's own numpy stream, k_search_load's seed + i). Without an evaluator and at eps = 0 the closed form
+    of the hash evaluator's row: every weight 2^-12, normalised in double, one rounding to float."""
+    if evaluate is None and eps == 0.0:
+        n = len(words)
+        return [F(np.float64(2.0 ** -12) / (np.float64(n) * np.float64(2.0 ** -12)))] * n, hash_value(st[:64])
+    logits, value = (evaluate or hash_eval)([st])[0]
+    return root_priors(logits, words, O.MT(seed, "numpy"), eps, alpha), F(value)
+
+
+def leaf_rows_of(evaluate, pending):
+    """[(priors, value)] of a sim-step's pending leaves [(state after getValidMoves, move words)], evaluated
+    together in descent order (the step's network batch). Without an evaluator the hash evaluator's closed
+    form: e = 1 for every move, their sum n."""
+    if evaluate is None:
+        return [([F(1.0) / F(len(w))] * len(w), hash_value(lst[:64])) for lst, w in pending]
+    if not pending:
+        return []
+    rows = evaluate([lst for lst, _ in pending])
+    assert len(rows) == len(pending)
+    return [(leaf_priors(lg, w), F(v)) for (lg, v), (_, w) in zip(rows, pending)]
+
+
+def search(state, sims, leaves=1, c_puct=1.5, ncap=None, evaluate=None, eps=0.0, alpha=0.3, seed=0):
+    """-> dict(status, visits, q, prior, moves, best, pv, steps, nn_rows, root_value, sims: the root's visits,
+    accepted: the descents each sim-step accepted). evaluate(list of states after getValidMoves) -> [(logits[4096] float32, value
+    float32)], None: the hash evaluator; seed: the position's own stream (the call's seed + its index)."""
     c = F(c_puct)
     ncap = sims + 2 if ncap is None else ncap
     state = np.array(state, dtype=np.int8)
-    term = dict(visits=[], q=[], prior=[], moves=[], best=-1, pv=[], steps=0, nn_rows=0, accepted=[])
+    term = dict(visits=[], q=[], prior=[], moves=[], best=-1, pv=[], steps=0, nn_rows=0, accepted=[], sims=0)
     if O.is_draw(state):
         return dict(term, status=DRAW, root_value=F(0.0))
     moves3, st = O.valid_moves(state)
@@ -92,8 +221,9 @@ def search(state, sims, leaves=1, c_puct=1.5, ncap=None):
             return dict(term, status=CHECKMATED, root_value=F(-1.0 if st[64] else 1.0))
         return dict(term, status=STALEMATE, root_value=F(0.0))
     n = len(moves3)
-    # k_mcts_root at eps = 0: every weight 2^-12, normalised in double, one rounding to float
-    root = _Node(st, move_words(st, moves3), F(np.float64(2.0 ** -12) / (np.float64(n) * np.float64(2.0 ** -12))))
+    words = move_words(st, moves3)
+    priors, root_value = fresh_root_row(evaluate, st, words, eps, alpha, seed)
+    root = _Node(st, words, priors)
     root_wtm = int(st[64])
     root_n, done, steps, leaf_rows, per_step = 1, 0, 0, 0, []
     sqt = [F(np.sqrt(np.float64(k))) for k in range(sims + 4)]
@@ -139,12 +269,14 @@ def search(state, sims, leaves=1, c_puct=1.5, ncap=None):
                 nd.V[j] += 1
             vroot += 1
             accepted.append(rec)
+        # the step's network batch: its pending leaves in descent order
+        batch = [(val[0], move_words(*val)) for _, pending, val in accepted if pending]
+        rows = iter(zip(batch, leaf_rows_of(evaluate, batch)))
         for path, pending, val in accepted:
             if pending:
-                lst, lm = val
-                v = hash_value(lst[:64])
+                (lst, lw), (lp, v) = next(rows)
                 leaf_node, leaf_j = path[-1]
-                leaf_node.child[leaf_j] = _Node(lst, move_words(lst, lm), F(1.0) / F(len(lm)))
+                leaf_node.child[leaf_j] = _Node(lst, lw, lp)
                 leaf_rows += 1
             else:
                 v = val
@@ -171,7 +303,7 @@ def search(state, sims, leaves=1, c_puct=1.5, ncap=None):
         node = node.child[j]
     return dict(status=SEARCHED, visits=visits, q=q, prior=list(root.P), moves=list(root.words),
                 best=visits.index(max(visits)), pv=pv, steps=steps, nn_rows=1 + leaf_rows, accepted=per_step,
-                root_value=hash_value(st[:64]))
+                root_value=root_value, sims=done)
 
 
 def oracle_positions(n_games, plies, sims, eval_fn=None, seed0=42):
@@ -194,3 +326,10 @@ def oracle_positions(n_games, plies, sims, eval_fn=None, seed0=42):
 def hash_positions():
     """3 games x 6 plies at 48 sims with the hash evaluator: the 18 positions both test files use."""
     return oracle_positions(3, 6, 48)
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_positions():
+    """The same 3 games x 6 plies at 48 sims played with the synthetic evaluator: other games, as the priors
+    differ."""
+    return oracle_positions(3, 6, 48, synthetic_eval_planes)

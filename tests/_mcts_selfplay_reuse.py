@@ -18,6 +18,7 @@ import numpy as np
 from oracle import oracle as O
 
 from tests import _mcts_search as S
+from tests._mcts_search import leaf_priors, policy_index, root_priors  # noqa: F401  (also this module's names)
 
 F = np.float32
 
@@ -49,52 +50,6 @@ def net_eval(eval_fn):
         lg, vl = np.asarray(lg, dtype=F).reshape(len(states), 4096), np.asarray(vl, dtype=F).reshape(-1)
         return [(lg[k], vl[k]) for k in range(len(states))]
     return ev
-
-
-def policy_index(word):
-    return (word & 63) * 64 + ((word >> 6) & 63)
-
-
-def root_priors(logits, words, np_mt, eps, alpha):
-    """k_mcts_root: softmax with det_expf over the 4,096 logits, the reference's mixed legal weights
-    (fp32 keep x p + fp64 eps x Dirichlet), normalised by their serial sum, one rounding to float."""
-    probs = O.softmax_det_4096(logits)
-    noise, _ = np_mt.dirichlet(alpha, 4096)
-    keep = F(1.0 - eps)
-    w = []
-    for wd in words:
-        idx = policy_index(wd)
-        w.append(np.float64(F(keep * probs[idx])) + np.float64(eps) * noise[idx])
-    total = np.float64(0.0)
-    for x in w:
-        total = total + x
-    n = len(words)
-    if total == 0.0:
-        return [F(1.0) / F(n)] * n
-    return [F(x / total) for x in w]
-
-
-def leaf_priors(logits, words):
-    """mcts_backup_slot: softmax over the legal moves' logits only; lane l sums entries l, l + 64, ... in
-    order, then the xor butterfly over the 64 lanes."""
-    lg = np.array([logits[policy_index(wd)] for wd in words], dtype=F)
-    n = len(lg)
-    mx = lg.max()
-    e = np.array([O.det_expf(float(F(x - mx))) for x in lg], dtype=F)
-    part = np.zeros(64, dtype=F)
-    for lane in range(64):
-        s = F(0.0)
-        for j in range(lane, n, 64):
-            s = F(s + e[j])
-        part[lane] = s
-    m = 32
-    while m >= 1:
-        part = (part + part[np.arange(64) ^ m]).astype(F)
-        m >>= 1
-    total = part[0]
-    if total > 0:
-        return (e / total).astype(F)
-    return np.full(n, F(1.0) / F(n), dtype=F)
 
 
 def _count_nodes(root):

@@ -1,12 +1,16 @@
 """Plain-Python restatement of search sessions (DESIGN.md "Search sessions",
 kv_search_advance / kv_search_continue in knightvision_amd/csrc/kv_search.hip)
-for the hash test evaluator: persistent trees over the oracle's rules with the
-scoring loop of tests/_mcts_search.py, advance (re-root on the played edge's
-child, or drop the tree) and the top-up continue. Every score is built from
-numpy float32 scalars in the kernel's operation order, so visits, q, priors and
-the principal variation must equal the device's bit for bit. Shared by
-tests/test_mcts_session_cpu.py and tests/test_mcts_session_gpu.py; not a test
-module itself."""
+for any evaluator (tests/_mcts_search.py's: a list of positions -> their logits
+and values; none: the hash test evaluator): persistent trees over the oracle's
+rules with the scoring loop of tests/_mcts_search.py, advance (re-root on the
+played edge's child, or drop the tree) and the top-up continue. A carried root
+keeps the priors its node was expanded with (the leaf softmax over the legal
+logits) and the value the evaluator gave it then; a dropped tree's root is
+built as kv_search builds one (k_mcts_root's priors at eps = 0). Every score is
+built from numpy float32 scalars in the kernel's operation order, so visits, q,
+priors and the principal variation must equal the device's bit for bit. Shared
+by the test_mcts_session_* modules and tests/test_mcts_search_net_gpu.py; not a
+test module itself."""
 import numpy as np
 
 from oracle import oracle as O
@@ -15,13 +19,14 @@ from tests import _mcts_search as S
 
 F = np.float32
 SEARCHED, CHECKMATED, STALEMATE, DRAW = S.SEARCHED, S.CHECKMATED, S.STALEMATE, S.DRAW
+_SESSION = object()  # search / resume: the session's own evaluator
 
 
 class _Node(S._Node):
     __slots__ = ("value",)
 
-    def __init__(self, state, words, prior, value):
-        super().__init__(state, words, prior)
+    def __init__(self, state, words, priors, value):
+        super().__init__(state, words, priors)
         self.value = value  # the evaluator's value of the position, kept for a later re-root
 
 
@@ -46,11 +51,11 @@ class _Tree:
         self.status = SEARCHED
         self._st, self._moves3 = st, moves3
 
-    def build_root(self):
-        n = self.n_moves
-        # k_mcts_root at eps = 0: every weight 2^-12, normalised in double, one rounding to float
-        prior = F(np.float64(2.0 ** -12) / (np.float64(n) * np.float64(2.0 ** -12)))
-        self.root = _Node(self._st, S.move_words(self._st, self._moves3), prior, S.hash_value(self._st[:64]))
+    def build_root(self, evaluate):
+        # k_mcts_root at eps = 0 on the position's own network row
+        words = S.move_words(self._st, self._moves3)
+        priors, value = S.fresh_root_row(evaluate, self._st, words)
+        self.root = _Node(self._st, words, priors, value)
         self.root_wtm = int(self._st[64])
         self.root_value = self.root.value
         self.root_n = 1
@@ -67,20 +72,25 @@ class _Tree:
 
 class Session:
     """search(sims, leaves) / advance(edges) / resume(sims, leaves) / tree_size(i) over n positions, as
-    engine.PositionSearch gives them. ncap: the engine's node capacity (max_sims + 2)."""
+    engine.PositionSearch gives them. ncap: the engine's node capacity (max_sims + 2). evaluate: the
+    evaluator of tests/_mcts_search.search (None: hash); search and resume take one for their call alone, as
+    the network's batch class is the call's."""
 
-    def __init__(self, states, c_puct=1.5, ncap=66):
+    def __init__(self, states, c_puct=1.5, ncap=66, evaluate=None):
         self.c = F(c_puct)
         self.ncap = ncap
+        self.evaluate = evaluate
         self.states = [np.array(s, dtype=np.int8) for s in states]
         self.trees = None
 
-    def search(self, sims, leaves=1):
+    def search(self, sims, leaves=1, evaluate=_SESSION):
+        ev = self.evaluate if evaluate is _SESSION else evaluate
         self.trees = [_Tree(s) for s in self.states]
-        return [self._run(t, sims, leaves)[0] for t in self.trees]
+        return [self._run(t, sims, leaves, ev)[0] for t in self.trees]
 
-    def resume(self, sims, leaves=1):
-        got = [self._run(t, sims, leaves) for t in self.trees]
+    def resume(self, sims, leaves=1, evaluate=_SESSION):
+        ev = self.evaluate if evaluate is _SESSION else evaluate
+        got = [self._run(t, sims, leaves, ev) for t in self.trees]
         return [r for r, _ in got], [k for _, k in got]
 
     def advance(self, edges):
@@ -111,14 +121,14 @@ class Session:
         nodes = self.trees[i].nodes() if self.trees[i].status == SEARCHED else []
         return len(nodes), sum((len(nd.words) + 15) & ~15 for nd in nodes)
 
-    def _run(self, t, sims, leaves):
+    def _run(self, t, sims, leaves, evaluate):
         """The top-up search of one tree -> (result dict as _mcts_search.search's, kept)."""
         if t.status != SEARCHED:
             return dict(status=t.status, visits=[], q=[], prior=[], moves=[], best=-1, pv=[], steps=0, nn_rows=0,
                         accepted=[], root_value=t.root_value, sims=0), 0
         root_row = 0
         if t.fresh:
-            t.build_root()
+            t.build_root(evaluate)
             root_row = 1
         c, root = self.c, t.root
         kept = t.root_n - 1
@@ -166,12 +176,14 @@ class Session:
                     nd.V[j] += 1
                 vroot += 1
                 accepted.append(rec)
+            # the step's network batch: its pending leaves in descent order
+            batch = [(val[0], S.move_words(*val)) for _, pending, val in accepted if pending]
+            rows = iter(zip(batch, S.leaf_rows_of(evaluate, batch)))
             for path, pending, val in accepted:
                 if pending:
-                    lst, lm = val
-                    v = S.hash_value(lst[:64])
+                    (lst, lw), (lp, v) = next(rows)
                     leaf_node, leaf_j = path[-1]
-                    leaf_node.child[leaf_j] = _Node(lst, S.move_words(lst, lm), F(1.0) / F(len(lm)), v)
+                    leaf_node.child[leaf_j] = _Node(lst, lw, lp, v)
                     leaf_rows += 1
                 else:
                     v = val

@@ -7,7 +7,8 @@
   sim-steps and network rows.
 * The real ChessNet at L = 1: the oracle with the HIP network's own rows of
   the batch class (tests/test_mcts_gpu.py's method); at L = 8 the properties
-  that hold without a reference.
+  that hold without a reference (the restatement with the network's rows at
+  L > 1: tests/test_mcts_search_net_gpu.py).
 * Terminal roots, errors, play.search_move."""
 import ctypes as C
 

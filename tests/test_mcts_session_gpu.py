@@ -8,7 +8,8 @@ knightvision_amd/csrc/kv_search.hip) on the GPU.
 * A dropped tree resumes exactly as kv_search searches the state after the
   move; a tree that already holds the visits runs no step; a long line stays
   inside the default pools; mixed edges in one call; errors.
-* The real ChessNet: the properties that need no reference.
+* The real ChessNet: the properties that need no reference (the restatement
+  with the network's rows: tests/test_mcts_search_net_gpu.py).
 * play.SearchSession."""
 import ctypes as C
 
@@ -22,6 +23,7 @@ from knightvision_amd.weights import synthetic_state_dict
 
 from tests import _mcts_search as S
 from tests import _mcts_session as SS
+from tests._mcts_compare import line as _line, same as _same, same_call as _same_call
 
 pytestmark = pytest.mark.gpu
 
@@ -34,48 +36,6 @@ def hash_search():
     with PositionSearch(synthetic_state_dict(42, "init"), max_positions=18, max_sims=64,
                         eval_mode=EVAL_HASH) as ps:
         yield ps
-
-
-def _bits(a):
-    return np.array(a, dtype=np.float32).view(np.uint32).tolist()
-
-
-def _same(row, r, tag):
-    """A device row against the restatement's result of the same call."""
-    n = len(r["visits"])
-    assert (row["status"], row["n_moves"], row["sims"]) == (r["status"], n, r["sims"]), tag
-    assert row["visits"][:n].tolist() == r["visits"] and (row["visits"][n:] == -1).all(), tag
-    assert row["moves"][:n].tolist() == r["moves"], tag
-    assert _bits(row["q"][:n]) == _bits(r["q"]) and _bits(row["prior"][:n]) == _bits(r["prior"]), tag
-    assert row["pv"][:row["pv_len"]].tolist() == r["pv"], tag
-    assert (row["steps"], row["nn_rows"], row["best"]) == (r["steps"], r["nn_rows"], r["best"]), tag
-    assert row["root_value"] == r["root_value"], tag
-    if n:
-        assert row["best_q"] == r["q"][r["best"]], tag
-
-
-def _same_call(ps, ses, rows, ref, tag):
-    for i, (row, r) in enumerate(zip(rows, ref)):
-        _same(row, r, f"{tag} tree {i}")
-        assert ps.tree_size(i) == ses.tree_size(i), f"{tag} tree {i}"
-
-
-def _line(ps, states, plan):
-    """search at plan[0], then advance(best) -> resume for every further (sims, leaves) of the plan."""
-    ses = SS.Session(states)
-    rows = ps.search(np.stack(states), *plan[0])
-    _same_call(ps, ses, rows, ses.search(*plan[0]), "search")
-    for ply, (sims, leaves) in enumerate(plan[1:]):
-        edges = rows["best"].astype(np.int32)  # -1 at a root that is not searched
-        after = ps.advance(edges)
-        assert np.array_equal(after, np.stack(ses.advance(edges.tolist()))), ply
-        for i in range(len(states)):
-            assert ps.tree_size(i) == ses.tree_size(i), (ply, i)
-        rows, kept = ps.resume(sims, leaves)
-        ref, ref_kept = ses.resume(sims, leaves)
-        assert kept.tolist() == ref_kept, ply
-        _same_call(ps, ses, rows, ref, f"ply {ply}")
-    return rows
 
 
 @pytest.mark.parametrize("leaves", [1, 8])

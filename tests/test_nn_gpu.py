@@ -162,10 +162,11 @@ def test_i8_digits_track_fp64_domain(variant, precision, tol):
         assert dp < tol and dv < tol / 10, (n, dp, dv)
 
 
-@pytest.mark.parametrize("B", [17, 300, 2048])
+@pytest.mark.parametrize("B", [1, 16, 17, 300, 2048])
 def test_legal_logits_equal_full_rows(B):
     """kv_net_forward_boards_legal (the MCTS leaves' policy: listed moves only,
-    one fmaf chain per move) equals the full policy_fc rows bit for bit."""
+    one fmaf chain per move) equals the full policy_fc rows bit for bit, in the
+    <= 16-board class (1, 16: a position search of few trees and leaves) and above."""
     from knightvision_amd.engine import packed_from
     from knightvision_amd.model import KVNet
     net = KVNet(0, packed_from(synthetic_state_dict(42, "peaked")))

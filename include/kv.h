@@ -426,6 +426,23 @@ int kv_dev_wino88i(int device, const double* V, int rows, const double* U, int K
  * wino88d_in_kernel's fp64 V and the slice kernel (bit-identical). */
 int kv_dev_wino88i32_out(int device, const float* M, int rows, const float* scale, const float* shift,
                          const float* resid, int fused, float* Y, int8_t* v_digits, int* v_exp);
+/* The front of the R3 tower (KV_ALGO_WINOGRAD88_I8R3): boards [nb][64] int8 piece codes (0 empty, 1-12), `rows`
+ * >= nb a multiple of 32 (the rows past nb are empty boards), conv1 as wT [9][12][256] ([tap][piece][cout]),
+ * folded BN scale / shift [256] -> conv2's V as 3 radix-256 digits in 96-byte row lines [100][8][rows][3][32] in
+ * the first 3/4 of v_digits ([100][8][rows][4][32] bytes; the rest comes back as the byte 0x55) and row exponents
+ * [100][rows]. fused 1: the product's one-kernel form (stem_r3_kernel); 0: stem_kernel<4>'s fp32 V256, then the
+ * slice kernel (bit-identical). */
+int kv_dev_tower_front(int device, const int8_t* boards, int nb, int rows, const float* wT, const float* scale,
+                       const float* shift, int fused, int8_t* v_digits, int* v_exp);
+/* The back end of the fp32 tower on int8 digits: the last residual block's output step and the heads. M
+ * [100][rows][512] fp32 (rows a multiple of 32), folded BN scale / shift [512], resid [rows][64][512], heads =
+ * head conv weights [3][512] (policy 0, policy 1, value) | their BN scale [3] | shift [3] | value_fc1 weight
+ * [512][64] | bias [512] | value_fc2 weight [512] | bias [1] -> pfeat [rows][128] (channel-major policy
+ * features) and value [rows]. fused bit 0: the product's one-kernel form (wino88_out_heads_kernel: the activation
+ * goes from the output transform to the heads through LDS, no X; with bit 1 the residual read non-temporally,
+ * as the tower runs it at 1,024+ boards); clear: wino88_out_kernel's X, then heads_kernel (bit-identical). */
+int kv_dev_tower_back(int device, const float* M, int rows, const float* scale, const float* shift,
+                      const float* resid, const float* heads, int fused, float* pfeat, float* value);
 /* KV_PREC_I8R4's output step: M [100][rows][512] fp64 (rows a multiple of 128), folded BN scale / shift,
  * resid or NULL -> Y [rows][64][512] and the next conv's V as 4 radix-256 digits in row lines
  * [100][16][rows][4][32] with row exponents [100][rows]. fused 1: the product's wino88i64r_out_kernel; 0:

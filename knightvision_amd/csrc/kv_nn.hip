@@ -293,18 +293,24 @@ __global__ __launch_bounds__(64) void splitk_reduce_kernel(const float* __restri
 // (c*64+sq, ai/model.py:65), value_fc1 + ReLU, value_fc2 + tanh (:70-73).
 // One board per 1,024-thread block: 16 lanes per pixel split its 512 channels
 // (32 each), so the board's 128 KB are read with 16 waves' loads in flight.
-__global__ __launch_bounds__(1024) void heads_kernel(const float* __restrict__ X, const float* __restrict__ hw,
-                                                     const float* __restrict__ hs, const float* __restrict__ hb,
-                                                     const float* __restrict__ v1wT, const float* __restrict__ v1b,
-                                                     const float* __restrict__ v2w, const float* __restrict__ v2b,
-                                                     float* __restrict__ pfeat, float* __restrict__ value) {
+// heads_board: the heads of board b from its activation xb ([64][512] fp32, in global memory -- heads_kernel --
+// or in LDS -- wino88_out_heads_kernel): one body, and every multiply-add an explicit fmaf (the contractions
+// the compiler chose for heads_kernel under -ffp-contract=fast; left to it, it fused other pairs when the
+// activation came from LDS -- a packed multiply, then adds -- and the two forms differed by ulps) with contraction
+// off for everything else in the body, so both round the same operations in the same order by construction.
+__device__ inline void heads_board(const float* xb, int b, const float* __restrict__ hw,
+                                   const float* __restrict__ hs, const float* __restrict__ hb,
+                                   const float* __restrict__ v1wT, const float* __restrict__ v1b,
+                                   const float* __restrict__ v2w, const float* __restrict__ v2b,
+                                   float* __restrict__ pfeat, float* __restrict__ value) {
+#pragma clang fp contract(off)  // the fmaf calls below are the only fused operations, in either form
     __shared__ float s_pf[128];
     __shared__ float s_v[64];
     __shared__ float s_h[512];
     __shared__ float s_red[8];
-    const int b = blockIdx.x, t = threadIdx.x;
+    const int t = threadIdx.x;
     const int p = t >> 4, q = t & 15;
-    const float* xp = X + ((size_t)b * 64 + p) * 512;
+    const float* xp = xb + (size_t)p * 512;
     float a0 = 0.f, a1 = 0.f, a2 = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -315,9 +321,9 @@ __global__ __launch_bounds__(1024) void heads_kernel(const float* __restrict__ X
         const f32x4 w2 = *(const f32x4*)(hw + 1024 + c);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            a0 += x[e] * w0[e];
-            a1 += x[e] * w1[e];
-            a2 += x[e] * w2[e];
+            a0 = __builtin_fmaf(x[e], w0[e], a0);
+            a1 = __builtin_fmaf(x[e], w1[e], a1);
+            a2 = __builtin_fmaf(x[e], w2[e], a2);
         }
     }
 #pragma unroll
@@ -327,7 +333,8 @@ __global__ __launch_bounds__(1024) void heads_kernel(const float* __restrict__ X
         a2 += __shfl_xor(a2, m);
     }
     if (q == 0) {
-        const float p0 = a0 * hs[0] + hb[0], p1 = a1 * hs[1] + hb[1], v = a2 * hs[2] + hb[2];
+        const float p0 = __builtin_fmaf(a0, hs[0], hb[0]), p1 = __builtin_fmaf(a1, hs[1], hb[1]),
+                    v = __builtin_fmaf(a2, hs[2], hb[2]);
         s_pf[p] = p0 > 0.f ? p0 : 0.f;
         s_pf[64 + p] = p1 > 0.f ? p1 : 0.f;
         s_v[p] = v > 0.f ? v : 0.f;
@@ -337,18 +344,57 @@ __global__ __launch_bounds__(1024) void heads_kernel(const float* __restrict__ X
     if (t < 512) {  // value_fc1 from its [k][o] copy: lanes read adjacent outputs
         float hsum = v1b[t];
 #pragma unroll 16
-        for (int k = 0; k < 64; ++k) hsum += v1wT[k * 512 + t] * s_v[k];
+        for (int k = 0; k < 64; ++k) hsum = __builtin_fmaf(v1wT[k * 512 + t], s_v[k], hsum);
         s_h[t] = hsum > 0.f ? hsum : 0.f;
     }
     __syncthreads();
     if (t < 256) {
-        float part = v2w[t] * s_h[t] + v2w[t + 256] * s_h[t + 256];
+        float part = __builtin_fmaf(v2w[t], s_h[t], v2w[t + 256] * s_h[t + 256]);
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m);
         if ((t & 63) == 0) s_red[t >> 6] = part;
     }
     __syncthreads();
     if (t == 0) value[b] = tanhf(s_red[0] + s_red[1] + s_red[2] + s_red[3] + v2b[0]);
+}
+
+__global__ __launch_bounds__(1024) void heads_kernel(const float* __restrict__ X, const float* __restrict__ hw,
+                                                     const float* __restrict__ hs, const float* __restrict__ hb,
+                                                     const float* __restrict__ v1wT, const float* __restrict__ v1b,
+                                                     const float* __restrict__ v2w, const float* __restrict__ v2b,
+                                                     float* __restrict__ pfeat, float* __restrict__ value) {
+    const int b = blockIdx.x;
+    heads_board(X + (size_t)b * 64 * 512, b, hw, hs, hb, v1wT, v1b, v2w, v2b, pfeat, value);
+}
+
+// The last residual block's output transform + BN + residual + ReLU (wino88_out_plane_half: the arithmetic of
+// wino88_out_kernel<true, true, false>, a plane split over lanes l and l ^ 32) with the heads on top: the board's
+// activation goes to LDS ([64][512] fp32, 128 KiB: the large-LDS opt-in) instead of X, and heads_board reads it
+// there -- the same lane-to-channel split and reduction order as heads_kernel over X, so pfeat and value are the
+// same bits, without X's round trip through HBM (128 KiB written and 128 KiB read per board). Nothing
+// else reads the tower's last X. One 1,024-thread workgroup per board (grid = the real boards: a padding board
+// has no heads); YNT: the residual read non-temporally (wino88_out_plane_half).
+constexpr int kOutHeadsLds = 64 * 512 * 4;
+template <bool YNT>
+__global__ __launch_bounds__(1024) void wino88_out_heads_kernel(
+    const float* __restrict__ M, int rows, const float* __restrict__ scale, const float* __restrict__ shift,
+    const float* __restrict__ resid, const float* __restrict__ hw, const float* __restrict__ hs,
+    const float* __restrict__ hb, const float* __restrict__ v1wT, const float* __restrict__ v1b,
+    const float* __restrict__ v2w, const float* __restrict__ v2b, float* __restrict__ pfeat,
+    float* __restrict__ value) {
+    extern __shared__ __attribute__((aligned(16))) float xs[];  // the board's activation [64][512]
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5;
+    const int c = w * 32 + (lane & 31), b = blockIdx.x;
+    {
+        float x2[4][8];  // pixels (4h + ii, j) of channel c
+        wino88_out_plane_half<true, false, false, 0, YNT>(M, rows, b, c, h, scale[c], shift[c], resid, nullptr, x2);
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xs[((4 * h + ii) * 8 + j) * 512 + c] = x2[ii][j];
+    }
+    __syncthreads();
+    heads_board(xs, b, hw, hs, hb, v1wT, v1b, v2w, v2b, pfeat, value);
 }
 
 // --------------------------------------------------------- policy fc --
@@ -816,6 +862,7 @@ static int net_reserve(kv_net* net, int nb_pad) {
 }
 
 static int net_heads(kv_net* net, int nb, float* policy, float* value, hipStream_t st);
+static int net_policy(kv_net* net, int nb, float* policy, hipStream_t st);
 
 // LDS_PAD: dynamic LDS requested beyond the tiles' need, to cap workgroups per CU
 template <int K, int WR, int WC, int MT, int NT, int CK, int LDS_PAD, int XI>
@@ -1488,9 +1535,49 @@ static int wino88i32_gemm_layer(kv_net* net, int l, int K, int rows, int stride,
     return KV_OK;
 }
 
+// The last block's output transform with the heads on top (wino88_out_heads_kernel): pfeat and value of boards
+// [0, nb) from M ([100][stride][512]) and the residual; X is not written. v1wT: value_fc1's weight as [k][o].
+static int launch_wino88_out_heads(const float* M, int nb, int stride, const float* sc, const float* sh,
+                                   const float* resid, const float* hw, const float* hs, const float* hb,
+                                   const float* v1wT, const float* v1b, const float* v2w, const float* v2b,
+                                   float* pfeat, float* value, bool ynt, hipStream_t st) {
+    // ynt: the residual read non-temporally (the tower: at 1,024+ boards, as the other output kernels)
+    auto kern = ynt ? kv::wino88_out_heads_kernel<true> : kv::wino88_out_heads_kernel<false>;
+    KV_HIP(lds_opt_in((const void*)kern, kv::kOutHeadsLds));
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(1024), kv::kOutHeadsLds, st, M, stride, sc, sh, resid, hw, hs, hb, v1wT,
+                       v1b, v2w, v2b, pfeat, value);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
+}
+
+// The R3 tower's front in one kernel (kv_wino88i.h stem_r3_kernel): conv2's V as 96-byte row-line digits and row
+// exponents straight from the board codes. One workgroup per CU (a multiple of 8 of them: out_board), each
+// looping over its boards with conv1 staged in LDS once.
+static int launch_stem_r3(const int8_t* boards, int nb, int rows, const float* stemT, const float* sc,
+                          const float* sh, int8_t* V8, int* ev, hipStream_t st) {
+    KV_REQUIRE(rows % 32 == 0 && nb <= rows, KV_EINVAL, "R3 stem: %d boards in %d rows (a multiple of 32: out_board)",
+               nb, rows);
+    const int cus = device_cus() & ~7;
+    const int grid = cus > 0 && cus < rows ? cus : rows;
+    KV_HIP(lds_opt_in((const void*)kv::stem_r3_kernel, kv::kStemR3Lds));
+    hipLaunchKernelGGL(kv::stem_r3_kernel, dim3(grid), dim3(512), kv::kStemR3Lds, st, boards, nb, rows, stemT, sc, sh,
+                       V8, ev);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
+}
+
+// Where the fused last output kernel puts the heads' value (nb: the real boards); absent: the last block writes X
+struct HeadsOut {
+    int nb;
+    float* value;
+};
+
 // v64 (KV_PATH_WINO88_I8F32V): conv2's V256 is fp64 (the stem's / wino88d_in_kernel's) and every output
 // kernel is wino88i32v_out_kernel (the slice and segment forms do not apply)
-static int wino88i32_blocks(kv_net* net, int nb, bool mark, bool v64, hipStream_t st, bool r3 = false) {
+// ho: the last block's output transform runs the heads too (net->pfeat, ho->value) and writes no X
+// v8_ready: conv2's digits and exponents are in V8 / ev8 already (stem_r3_kernel): no slice pass over V256
+static int wino88i32_blocks(kv_net* net, int nb, bool mark, bool v64, hipStream_t st, bool r3 = false,
+                            const HeadsOut* ho = nullptr, bool v8_ready = false) {
     const int rows = nb, stride = rows;
     float* V = (float*)net->V;
     const float* M = (const float*)net->Mw;
@@ -1498,7 +1585,7 @@ static int wino88i32_blocks(kv_net* net, int nb, bool mark, bool v64, hipStream_
     int8_t* V8 = net->V8;
     int* ev = net->ev8;
     int rc;
-    if ((rc = wino88i32_gemm_layer(net, 1, 256, rows, stride, true, false, v64, st, r3))) return rc;
+    if ((rc = wino88i32_gemm_layer(net, 1, 256, rows, stride, !v8_ready, false, v64, st, r3))) return rc;
     rc = v64  ? launch_wino88i32v_out<false, true>(net, 1, M, nb, stride, nullptr, net->X, V8, ev, st)
          : sf ? launch_wino88_out<false, true, true>(net, 1, M, nb, stride, nullptr, net->X, V, st)
               : launch_wino88i32_out<false, true>(net, 1, M, nb, stride, nullptr, net->X, V8, ev, seg, st, r3);
@@ -1513,7 +1600,13 @@ static int wino88i32_blocks(kv_net* net, int nb, bool mark, bool v64, hipStream_
                   : launch_wino88i32_out<false, false>(net, l1, M, nb, stride, nullptr, nullptr, V8, ev, seg, st, r3);
         if (rc) return rc;
         if ((rc = wino88i32_gemm_layer(net, l2, 512, rows, stride, sf, false, v64, st, r3))) return rc;
-        if (r == 4)
+        if (r == 4 && ho) {
+            const float* W = net->w;
+            const kv::PackOffsets& o = net->off;
+            rc = launch_wino88_out_heads(M, ho->nb, stride, W + o.scale[l2], W + o.shift[l2], net->X, W + o.head_w,
+                                         W + o.head_scale, W + o.head_shift, net->v1wT, W + o.vfc1_b, W + o.vfc2_w,
+                                         W + o.vfc2_b, net->pfeat, ho->value, ho->nb >= 1024, st);
+        } else if (r == 4)
             rc = launch_wino88_out<true, true, false>(net, l2, M, nb, stride, net->X, net->X, nullptr, st);
         else
             rc = v64  ? launch_wino88i32v_out<true, true>(net, l2, M, nb, stride, net->X, net->X, V8, ev, st)
@@ -1567,7 +1660,10 @@ static int net_reserve_ws(kv_net* net, int path) {
 
 // Winograd tower on `path`: conv2 and the 5 residual blocks (conv1 output in
 // net->T, or conv2's input transform already in net->V256 when v256_ready)
-static int net_tower_wino(kv_net* net, int nb_pad, int path, bool v256_ready, hipStream_t st) {
+// ho (the fp32 tower on int8 digits only): the last output kernel runs the heads too (wino88i32_blocks)
+// v8_ready (KV_PATH_WINO88_I8F32R3): the stem wrote conv2's digits itself (no V256)
+static int net_tower_wino(kv_net* net, int nb_pad, int path, bool v256_ready, hipStream_t st,
+                          const HeadsOut* ho = nullptr, bool v8_ready = false) {
     int rc;
     net->dom_path = path;
     net->dom_launches = 1;
@@ -1577,7 +1673,7 @@ static int net_tower_wino(kv_net* net, int nb_pad, int path, bool v256_ready, hi
         path == KV_PATH_WINO88_I8F32R3) {
         const bool f64 = path == KV_PATH_WINO88_F64 || path == KV_PATH_WINO88_I8 || path == KV_PATH_WINO88_I8R ||
                          path == KV_PATH_WINO88_I8F32V;
-        if (!v256_ready) {
+        if (!v256_ready && !v8_ready) {
             if (f64)
                 hipLaunchKernelGGL(kv::wino88d_in_kernel<256>, dim3(1, nb_pad), dim3(256), 0, st, net->T, nb_pad,
                                    (double*)net->V256);
@@ -1586,9 +1682,9 @@ static int net_tower_wino(kv_net* net, int nb_pad, int path, bool v256_ready, hi
                                    (float*)net->V256);
             KV_HIP(hipGetLastError());
         }
-        if ((rc = path == KV_PATH_WINO88_I8F32    ? wino88i32_blocks(net, nb_pad, true, false, st)
-                  : path == KV_PATH_WINO88_I8F32R3 ? wino88i32_blocks(net, nb_pad, true, false, st, true)
-                  : path == KV_PATH_WINO88_I8F32V ? wino88i32_blocks(net, nb_pad, true, true, st)
+        if ((rc = path == KV_PATH_WINO88_I8F32    ? wino88i32_blocks(net, nb_pad, true, false, st, false, ho)
+                  : path == KV_PATH_WINO88_I8F32R3 ? wino88i32_blocks(net, nb_pad, true, false, st, true, ho, v8_ready)
+                  : path == KV_PATH_WINO88_I8F32V ? wino88i32_blocks(net, nb_pad, true, true, st, false, ho)
                   : path == KV_PATH_WINO88_I8  ? wino88i_blocks(net, nb_pad, true, false, st)
                   : path == KV_PATH_WINO88_I8R ? wino88i_blocks(net, nb_pad, true, true, st)
                   : path == KV_PATH_WINO88_F64 ? wino88d_blocks(net, nb_pad, true, st)
@@ -1618,8 +1714,15 @@ static int net_tower(kv_net* net, int nb, int nb_pad, const int8_t* boards, floa
     if ((rc = net_reserve_ws(net, path))) return rc;
     if (tm) KV_HIP(hipEventRecord(net->ev[0], st));
     // Winograd paths: the stem builds conv2's V itself
-    bool v256_ready = false;
-    if (boards) {
+    bool v256_ready = false, v8_ready = false;
+    // the stem writes conv2's R3 digits itself, no V256: at large batches (121 against 60 + 76 us at 2,048 boards;
+    // at 128 boards the forward measured 1.6 % slower with it, so small batches keep the stem + slice pair)
+    if (boards && path == KV_PATH_WINO88_I8F32R3 && nb_pad >= 1024) {
+        if ((rc = launch_stem_r3(boards, nb, nb_pad, net->stemT, W + o.scale[0], W + o.shift[0], net->V8, net->ev8,
+                                 st)))
+            return rc;
+        v8_ready = true;
+    } else if (boards) {
         if (path == KV_PATH_WINO88 || path == KV_PATH_WINO88_I8F32 || path == KV_PATH_WINO88_I8F32R3)
             hipLaunchKernelGGL(kv::stem_kernel<4>, dim3(4, nb_pad / 2), dim3(256), 0, st, boards, nb, net->stemT,
                                W + o.scale[0], W + o.shift[0], (float*)net->V256, nb_pad, nullptr);
@@ -1637,6 +1740,12 @@ static int net_tower(kv_net* net, int nb, int nb_pad, const int8_t* boards, floa
         return rc;
     }
     if (path_is_wino(path)) {
+        // the fp32 tower on int8 digits: the last block's output kernel feeds the heads through LDS (no X)
+        if (path == KV_PATH_WINO88_I8F32 || path == KV_PATH_WINO88_I8F32R3 || path == KV_PATH_WINO88_I8F32V) {
+            const HeadsOut ho = {nb, value};
+            if ((rc = net_tower_wino(net, nb_pad, path, v256_ready, st, &ho, v8_ready))) return rc;
+            return net_policy(net, nb, policy, st);
+        }
         if ((rc = net_tower_wino(net, nb_pad, path, v256_ready, st))) return rc;
         return net_heads(net, nb, policy, value, st);
     }
@@ -1671,6 +1780,13 @@ static int net_heads(kv_net* net, int nb, float* policy, float* value, hipStream
     hipLaunchKernelGGL(kv::heads_kernel, dim3(nb), dim3(1024), 0, st, net->X, W + o.head_w, W + o.head_scale,
                        W + o.head_shift, net->v1wT, W + o.vfc1_b, W + o.vfc2_w, W + o.vfc2_b, net->pfeat, value);
     KV_HIP(hipGetLastError());
+    return net_policy(net, nb, policy, st);
+}
+
+// the policy's logits from net->pfeat
+static int net_policy(kv_net* net, int nb, float* policy, hipStream_t st) {
+    const float* W = net->w;
+    const kv::PackOffsets& o = net->off;
     if (net->legal.out) {  // kv_net_forward_boards_legal: the listed moves' logits only
         hipLaunchKernelGGL(kv::policy_legal_kernel, dim3(nb), dim3(64), 0, st, net->pfeat, W + o.pfc_w, W + o.pfc_b,
                            net->legal.moves, net->legal.n, net->legal.maxm, net->legal.out);
@@ -2366,6 +2482,91 @@ int kv_dev_wino88i32_out(int device, const float* M, int rows, const float* scal
     KV_HIP(hipMemcpy(Y, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
     KV_HIP(hipMemcpy(v_digits, v8.p, nm * kv::kI8DigitsF32, hipMemcpyDeviceToHost));
     KV_HIP(hipMemcpy(v_exp, ev.p, (size_t)kv::W88_XI * rows * (seg ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost));
+    return KV_OK;
+}
+
+int kv_dev_tower_front(int device, const int8_t* boards, int nb, int rows, const float* wT, const float* scale,
+                       const float* shift, int fused, int8_t* v_digits, int* v_exp) {
+    KV_REQUIRE(boards && wT && scale && shift && v_digits && v_exp && nb > 0 && nb <= rows && rows % 32 == 0 &&
+                   rows <= kMaxBoards,
+               KV_EINVAL, "kv_dev_tower_front: bad arguments (%d boards in %d rows: a multiple of 32, at most %d)", nb,
+               rows, kMaxBoards);
+    KV_HIP(hipSetDevice(device));
+    const size_t nv = (size_t)kv::W88_XI * rows * 256, nd = nv * kv::kI8DigitsF32;
+    kv::DevBuf<int8_t> db, v8;
+    kv::DevBuf<float> dw, dsc, dsh, dv;
+    kv::DevBuf<int> ev;
+    KV_HIP(db.alloc((size_t)nb * 64));
+    KV_HIP(dw.alloc(9 * 12 * 256));
+    KV_HIP(dsc.alloc(256));
+    KV_HIP(dsh.alloc(256));
+    KV_HIP(v8.alloc(nd));
+    KV_HIP(ev.alloc((size_t)kv::W88_XI * rows));
+    KV_HIP(hipMemset(v8.p, 0x55, nd));  // the lines fill the first 3/4; the rest must come back as it is
+    KV_HIP(hipMemcpy(db.p, boards, (size_t)nb * 64, hipMemcpyHostToDevice));
+    KV_HIP(hipMemcpy(dw.p, wT, 9 * 12 * 256 * sizeof(float), hipMemcpyHostToDevice));
+    KV_HIP(hipMemcpy(dsc.p, scale, 256 * sizeof(float), hipMemcpyHostToDevice));
+    KV_HIP(hipMemcpy(dsh.p, shift, 256 * sizeof(float), hipMemcpyHostToDevice));
+    if (fused) {
+        const int rc = launch_stem_r3(db.p, nb, rows, dw.p, dsc.p, dsh.p, v8.p, ev.p, 0);
+        if (rc) return rc;
+    } else {  // conv2's fp32 V256, then its digits
+        KV_HIP(dv.alloc(nv));
+        hipLaunchKernelGGL(kv::stem_kernel<4>, dim3(4, rows / 2), dim3(256), 0, 0, db.p, nb, dw.p, dsc.p, dsh.p, dv.p,
+                           rows, nullptr);
+        KV_HIP(hipGetLastError());
+        const int rc = launch_wino88i_slice<256, kv::kI8DigitsF32, float, 1, false, true>(dv.p, rows, rows, kv::W88_XI,
+                                                                                          v8.p, ev.p, 0);
+        if (rc) return rc;
+    }
+    KV_HIP(hipDeviceSynchronize());
+    KV_HIP(hipMemcpy(v_digits, v8.p, nd, hipMemcpyDeviceToHost));
+    KV_HIP(hipMemcpy(v_exp, ev.p, (size_t)kv::W88_XI * rows * sizeof(int), hipMemcpyDeviceToHost));
+    return KV_OK;
+}
+
+int kv_dev_tower_back(int device, const float* M, int rows, const float* scale, const float* shift,
+                      const float* resid, const float* heads, int fused, float* pfeat, float* value) {
+    KV_REQUIRE(M && scale && shift && resid && heads && pfeat && value && rows > 0 && rows % 32 == 0 &&
+                   rows <= kMaxBoards,
+               KV_EINVAL, "kv_dev_tower_back: bad arguments (rows %d: a multiple of 32, at most %d)", rows,
+               kMaxBoards);
+    KV_HIP(hipSetDevice(device));
+    const size_t nm = (size_t)kv::W88_XI * rows * 512, ny = (size_t)rows * 64 * 512;
+    constexpr size_t kHeads = 3 * 512 + 3 + 3 + 512 * 64 + 512 + 512 + 1;
+    kv::DevBuf<float> dm, dsc, dsh, dy, dh, dwT, dpf, dval;
+    KV_HIP(dm.alloc(nm));
+    KV_HIP(dsc.alloc(512));
+    KV_HIP(dsh.alloc(512));
+    KV_HIP(dy.alloc(ny));
+    KV_HIP(dh.alloc(kHeads));
+    KV_HIP(dwT.alloc(64 * 512));
+    KV_HIP(dpf.alloc((size_t)rows * 128));
+    KV_HIP(dval.alloc(rows));
+    KV_HIP(hipMemcpy(dm.p, M, nm * sizeof(float), hipMemcpyHostToDevice));
+    KV_HIP(hipMemcpy(dsc.p, scale, 512 * sizeof(float), hipMemcpyHostToDevice));
+    KV_HIP(hipMemcpy(dsh.p, shift, 512 * sizeof(float), hipMemcpyHostToDevice));
+    KV_HIP(hipMemcpy(dy.p, resid, ny * sizeof(float), hipMemcpyHostToDevice));
+    KV_HIP(hipMemcpy(dh.p, heads, kHeads * sizeof(float), hipMemcpyHostToDevice));
+    const float *hw = dh.p, *hs = hw + 3 * 512, *hb = hs + 3, *v1w = hb + 3, *v1b = v1w + 512 * 64,
+                *v2w = v1b + 512, *v2b = v2w + 512;
+    hipLaunchKernelGGL(kv::transpose_v1_kernel, dim3(64 * 512 / 256), dim3(256), 0, 0, v1w, dwT.p);
+    KV_HIP(hipGetLastError());
+    if (fused) {
+        const int rc = launch_wino88_out_heads(dm.p, rows, rows, dsc.p, dsh.p, dy.p, hw, hs, hb, dwT.p, v1b, v2w, v2b,
+                                               dpf.p, dval.p, (fused & 2) != 0, 0);
+        if (rc) return rc;
+    } else {  // X in place over the residual, as the tower ran it, then the heads over X
+        hipLaunchKernelGGL((kv::wino88_out_kernel<true, true, false>), dim3(512 / 256, rows), dim3(256), 0, 0, dm.p,
+                           rows, dsc.p, dsh.p, dy.p, dy.p, nullptr);
+        KV_HIP(hipGetLastError());
+        hipLaunchKernelGGL(kv::heads_kernel, dim3(rows), dim3(1024), 0, 0, dy.p, hw, hs, hb, dwT.p, v1b, v2w, v2b,
+                           dpf.p, dval.p);
+        KV_HIP(hipGetLastError());
+    }
+    KV_HIP(hipDeviceSynchronize());
+    KV_HIP(hipMemcpy(pfeat, dpf.p, (size_t)rows * 128 * sizeof(float), hipMemcpyDeviceToHost));
+    KV_HIP(hipMemcpy(value, dval.p, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost));
     return KV_OK;
 }
 

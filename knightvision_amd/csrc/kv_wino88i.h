@@ -2121,6 +2121,110 @@ __global__ __launch_bounds__(2 * CW) void wino88i32_out_kernel(const float* __re
     }
 }
 
+// stem_r3_kernel: the front of the R3 tower in one kernel -- conv1 + BN + ReLU straight from the int8 board codes
+// (stem_kernel<4>'s arithmetic: the occupied 3x3 neighbours' weights added in tap order, one fmaf for the folded
+// BN, as the compiler contracts it there), conv2's input transform by lane swaps (wino88_input_cols / _row, as
+// wino88_input_half), then wino88i32_out_kernel's back half at 256 channels: row maxima (DPP, then LDS over the 8
+// waves), i8_row_exponent_f32r, i8_digits_r3, the quad byte transpose, 96-byte row lines [100][8][rows][3][32] and
+// exponents [100][rows] -- what stem_kernel<4>'s fp32 V256 followed by wino88i_slice_kernel<256, float, 4, true, 1,
+// false, true> gives, bit for bit, without V256's HBM round trip (105 KB written and read per board).
+// 512 threads = a board's 256 channels, a plane split over lanes l and l ^ 32. conv1 ([code 0..12][tap][256], code
+// 0 = empty = zero rows: 117 KiB) is staged in LDS once per workgroup, and the workgroup loops over boards
+// out_board(blockIdx.x + k gridDim.x): with gridDim.x a multiple of 8, every id it runs has its own id mod 8, so
+// the 4 boards that share 128-byte lines stay on one XCD (out_board). Boards >= nb are empty (padding rows).
+constexpr int kStemR3Lds = 9 * 13 * 256 * 4;
+__global__ __launch_bounds__(512) void stem_r3_kernel(const int8_t* __restrict__ boards, int nb, int rows,
+                                                      const float* __restrict__ wT, const float* __restrict__ scale,
+                                                      const float* __restrict__ shift, int8_t* __restrict__ V8,
+                                                      int* __restrict__ ex) {
+#pragma clang fp contract(off)
+    constexpr int NK = 256 / 32, NW = 8;
+    extern __shared__ __attribute__((aligned(16))) float stem_wl[];  // [13][9][256]
+    // the board with a one-square empty border (10x10), each code as its table offset: a square's address (+ the
+    // lane's channel) is computed once for the up to 9 taps that read it, the tap an immediate offset
+    __shared__ int codes[100];
+    __shared__ __attribute__((aligned(16))) unsigned red[NW][2][5][16];
+    __shared__ int exs[100];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5;
+    const int c = w * 32 + (lane & 31);
+    for (int i = threadIdx.x; i < 9 * 13 * 256; i += 512) {
+        const int r = i >> 8, code = r / 9, t = r % 9;
+        stem_wl[i] = code ? wT[(size_t)(t * 12 + code - 1) * 256 + (i & 255)] : 0.f;
+    }
+    const float sc = scale[c], sh = shift[c];
+    const int q = lane & 3;
+    unsigned* const dst = (unsigned*)V8;
+    const unsigned xstride = NK * (unsigned)rows * 96u;
+    for (int id = blockIdx.x; id < rows; id += gridDim.x) {
+        const int b = out_board<true>(id);
+        __syncthreads();  // the table staged; the previous board's codes and exponents read
+        if (threadIdx.x < 100) {
+            const int i = threadIdx.x, r = i / 10 - 1, f = i % 10 - 1;
+            const bool in = b < nb && r >= 0 && r < 8 && f >= 0 && f < 8;
+            codes[i] = in ? boards[(size_t)b * 64 + r * 8 + f] * (9 * 256) : 0;
+        }
+        __syncthreads();
+        float vk[5][10];  // this half's 50 V values (rows 5h .. 5h+4), kept across the exponent barrier
+        {
+            float t2[10][4];
+            {
+                float x2[4][8];
+#pragma unroll
+                for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+                    for (int px = 0; px < 8; ++px) {
+                        const int py = 4 * h + ii;
+                        float acc = 0.f;
+#pragma unroll
+                        for (int t = 0; t < 9; ++t)
+                            acc += stem_wl[codes[(py + t / 3) * 10 + px + t % 3] + t * 256 + c];
+                        const float v = __builtin_fmaf(acc, sc, sh);
+                        x2[ii][px] = v > 0.f ? v : 0.f;
+                    }
+                wino88_input_cols(x2, h, t2);
+            }
+#pragma unroll
+            for (int aa = 0; aa < 5; ++aa) wino88_input_row(t2, h, aa, vk[aa]);
+        }
+#pragma unroll
+        for (int aa = 0; aa < 5; ++aa) {
+            unsigned m[10];
+#pragma unroll
+            for (int bb = 0; bb < 10; ++bb) m[bb] = i8_half_max_dpp(__float_as_uint(vk[aa][bb]) & 0x7fffffffu);
+            if ((lane & 31) == 16) {  // this half's 10 maxima, written by one lane
+                uint4* rr = (uint4*)&red[w][h][aa][0];
+                rr[0] = make_uint4(m[0], m[1], m[2], m[3]);
+                rr[1] = make_uint4(m[4], m[5], m[6], m[7]);
+                *(uint2*)&red[w][h][aa][8] = make_uint2(m[8], m[9]);
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < 100) {
+            const int xi = threadIdx.x, a = xi / 10, bb = xi % 10, hh = a / 5, aa = a % 5;
+            unsigned m = 0;
+#pragma unroll
+            for (int ww = 0; ww < NW; ++ww) m = red[ww][hh][aa][bb] > m ? red[ww][hh][aa][bb] : m;
+            const int e = i8_row_exponent_f32r(m);
+            exs[xi] = e;
+            ex[(size_t)xi * rows + b] = e;
+        }
+        __syncthreads();
+        // row line (xi, kc = c / 32, b): 96 bytes, digit d of channel 32 kc + i at byte 32 d + i
+        const unsigned off0 = ((unsigned)(c >> 5) * rows + b) * 96u + q * 32 + (c & 28);
+#pragma unroll
+        for (int aa = 0; aa < 5; ++aa) {
+            const int a = 5 * h + aa;
+#pragma unroll
+            for (int bb = 0; bb < 10; ++bb) {
+                const int xi = a * 10 + bb;
+                const unsigned P = i8_digits_r3((double)vk[aa][bb], exs[xi]);
+                const unsigned T4 = i8_quad_transpose(P, lane);  // lane q of the quad: digit q's 4 channels
+                if (q < 3) dst[(off0 + (unsigned)xi * xstride) >> 2] = T4;  // ordinary stores, merged in L2
+            }
+        }
+    }
+}
+
 // wino88i32_outp_kernel: wino88i32_out_kernel<RESID, WRITE_Y, 512, R3>'s result, bit for bit, as a persistent
 // kernel that streams M through LDS by DMA. One 1,024-thread workgroup per CU loops over its boards (blockIdx.x,
 // + gridDim.x, ...); a board's output transform runs in 5 column steps, step jj reading M's points i*10 + jj and

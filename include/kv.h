@@ -205,6 +205,12 @@ typedef struct {
                              expansion that does not fit raises KV_EOVERFLOW (kv_stats.tree_overflows) */
     int keep_root_visits; /* 1: keep each MCTS move's root visit counts (pi) for kv_root_visits[_device];
                              2: as 1, and also each committed move's root move words for kv_root_moves[_device] */
+    int sim_groups;       /* MCTS self-play: the slot groups a move's sim loop runs as, each group's chain (leaf forward,
+                             backup + select) on a stream of its own with its own network workspaces, so that one
+                             group's GEMM runs beside the other's output kernels (DESIGN.md "MCTS semantics"). 0: auto
+                             (kv_sim_groups_for), 1: one group, 2: two groups of slots / 2 (needs sims >= 1 and more
+                             than 16 slots per group, else KV_EINVAL). Records, root visits and stats are the same bit
+                             for bit. kv_search* always runs as one group */
     int reuse_tree;       /* MCTS self-play (sims >= 1): 0: every ply's tree is built from nothing; 1: the subtree
                              under the move just played is carried into the next ply (DESIGN.md "MCTS semantics",
                              "Carried subtrees in self-play"): its visits count toward sims, the root takes the
@@ -271,6 +277,9 @@ typedef struct {
 typedef struct kv_engine kv_engine;
 
 int kv_create(const kv_config* cfg, kv_engine** out);
+/* the slot groups an engine created from cfg runs (kv_config.sim_groups with 0 resolved; no GPU is touched), or
+ * KV_EINVAL for a sim_groups kv_create refuses */
+int kv_sim_groups_for(const kv_config* cfg);
 /* Loads the network weights; under fp32 + KV_ALGO_AUTO this runs the conv-path
  * calibration (kv_net_calibration), reported by kv_engine_calibration. */
 int kv_load_weights(kv_engine* e, const float* packed, size_t n_floats);
@@ -449,6 +458,14 @@ int kv_dev_tower_back(int device, const float* M, int rows, const float* scale, 
  * wino88d_out_half_kernel's Y, wino88d_in_kernel's fp64 V, the radix-256 slice kernel (bit-identical). */
 int kv_dev_wino88r_out(int device, const double* M, int rows, const float* scale, const float* shift,
                        const float* resid, int fused, float* Y, int8_t* v_digits, int* v_exp);
+/* Two nets with the same weights run side by side, each forward on a stream of its own (the probe of a two-group
+ * sim-step, tools/two_stream_forward_probe.py). cu_share 2: the R3 GEMM of either net sizes its grid for half the
+ * CUs (the one-round form when its tiles fill whole rounds of them), so two GEMMs in flight fill the chip once and
+ * a GEMM leaves half of it to the other net's output kernel; 1: the whole chip, as a net alone. follow 1: b's GEMM
+ * of every conv waits (stream-side, no host sync) for a's GEMM of the same conv in the forward enqueued before it,
+ * so b runs half a layer behind a; the caller enqueues a's forward first, then b's. Outputs are unchanged. A
+ * destroyed `a` must not stay b's leader: pair again (follow 0) or destroy b first. */
+int kv_dev_net_pair(kv_net* a, kv_net* b, int cu_share, int follow);
 /* Timing / A-B harness of the fp32 tower's int8-digit GEMM on seeded random digits (rows boards, K 256 or
  * 512): variant 0 the round-4 kernel, 1.. round-5 forms (persistent / per-tile, k per stage, ring depth);
  * avg_us = mean HIP-event time of `iters` launches; M_out [100][rows][512] (optional) for a bit-for-bit

@@ -21,7 +21,7 @@ class Config(C.Structure):
                 ("max_moves", C.c_int), ("batch", C.c_int), ("eps", C.c_double), ("alpha", C.c_double),
                 ("sims", C.c_int), ("c_puct", C.c_float), ("eval_mode", C.c_int), ("record_cap", C.c_int64),
                 ("recycle", C.c_int), ("precision", C.c_int), ("algo", C.c_int), ("tree_edge_cap", C.c_int),
-                ("keep_root_visits", C.c_int), ("reuse_tree", C.c_int)]
+                ("keep_root_visits", C.c_int), ("sim_groups", C.c_int), ("reuse_tree", C.c_int)]
 
 
 class Record(C.Structure):
@@ -113,6 +113,7 @@ def _declare(L):
         "kv_net_calibration": ([vp, P(Calib)], i),
         "kv_engine_calibration": ([vp, P(Calib)], i),
         "kv_create": ([P(Config), P(vp)], i),
+        "kv_sim_groups_for": ([P(Config)], i),
         "kv_load_weights": ([vp, P(C.c_float), sz], i),
         "kv_run": ([vp, i64, i64], i),
         "kv_set_max_moves": ([vp, i], i),
@@ -143,6 +144,7 @@ def _declare(L):
         "kv_dev_wino88i": ([i, P(C.c_double), i, P(C.c_double), i, i, i, P(C.c_double), P(C.c_int8), P(i)], i),
         "kv_dev_i8gemm_bench": ([i, i, i, i, i, P(C.c_float), P(C.c_float)], i),
         "kv_dev_gemm_clock": ([i, i, i, C.c_double, P(C.c_double)], i),
+        "kv_dev_net_pair": ([vp, vp, i, i], i),
         "kv_dev_out_phases": ([i, i, i, i, P(C.c_uint64), P(C.c_float)], i),
         "kv_dev_wino88i32_out": ([i, P(C.c_float), i, P(C.c_float), P(C.c_float), P(C.c_float), i, P(C.c_float),
                                   P(C.c_int8), P(i)], i),
@@ -187,12 +189,12 @@ def _declare(L):
 EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create", "kv_net_load", "kv_net_forward",
             "kv_net_forward_boards", "kv_net_forward_boards_legal", "kv_net_set_timing", "kv_net_last_timing", "kv_net_destroy", "kv_net_set_precision", "kv_net_set_algo",
             "kv_net_calibration", "kv_engine_calibration",
-            "kv_create",
+            "kv_create", "kv_sim_groups_for",
             "kv_load_weights", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_sizeof_config", "kv_sizeof_stats", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
             "kv_search", "kv_sizeof_search_result", "kv_search_advance", "kv_search_continue", "kv_search_tree_size",
             "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm",
             "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_tower_front", "kv_dev_tower_back", "kv_dev_i8gemm_bench",
-            "kv_dev_gemm_clock", "kv_dev_out_phases",
+            "kv_dev_gemm_clock", "kv_dev_out_phases", "kv_dev_net_pair",
             "kv_pgn_extract", "kv_fen_codes", "kv_san_move_index", "kv_chess_perft", "kv_chess_san", "kv_chess_fen",
             "kv_tr_conv3x3_f16", "kv_tr_conv3x3_add_f16", "kv_tr_conv_weights_f16", "kv_tr_wgrad_workspace", "kv_tr_conv3x3_wgrad_f16",
             "kv_tr_bn_workspace", "kv_tr_bn_stats_f16", "kv_tr_bn_apply_f16", "kv_tr_bn_backward_f16",

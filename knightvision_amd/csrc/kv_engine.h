@@ -19,6 +19,9 @@ int net_forward_boards_internal(kv_net* net, const int8_t* boards_dev, int B, fl
 int net_forward_boards_legal_internal(kv_net* net, const int8_t* boards_dev, int B, const uint16_t* moves,
                                       const int* n_moves, int maxm, float* legal, float* value, hipStream_t st);
 int net_set_res_events(kv_net* net, hipEvent_t a, hipEvent_t b);
+int net_view_create(kv_net* parent, kv_net** out);
+void net_view_destroy(kv_net* v);
+void net_set_cu_share(kv_net* net, int share);
 void net_dom_info(const kv_net* net, int* algo, int* launches, double* flop, int* path, int* split,
                   const char** kernel);
 

@@ -482,6 +482,14 @@ struct kv_engine {
     // (kv_destroy) waits for that copy on e->st
     hipEvent_t copy_done = nullptr;
     bool copy_pending = false;
+    // slot groups of the MCTS sim loop (kv_config.sim_groups resolved: 1 or 2). Two groups: slots [0, S / 2) on
+    // the engine stream with the engine's net, the rest on g_st with g_net, a view of that net (its own
+    // workspaces, made at the first kv_run after a weight load); g_fork / g_join order the two streams at the
+    // ends of a move's sim loop
+    int groups = 1;
+    hipStream_t g_st = nullptr;
+    hipEvent_t g_fork = nullptr, g_join = nullptr;
+    kv_net* g_net = nullptr;
     // kv_search: an engine serves either kv_run or kv_search (used: 0 neither yet, 1 kv_run, 2 kv_search)
     int used = 0;
     kv::SearchWs sw = {};
@@ -555,7 +563,24 @@ static int eng_collect_timing(kv_engine* e) {
     return KV_OK;
 }
 
+// kv_config.sim_groups resolved: 0 (auto) is two groups from 2,048 slots in MCTS mode -- each group then keeps
+// the fused R3 stem's 1,024-board floor and the GEMM's one-round grid on half the CUs -- else one
+static int sim_groups_for(const kv_config* cfg) {
+    if (cfg->sim_groups == 0) return cfg->sims > 0 && cfg->slots >= 2048 ? 2 : 1;
+    return cfg->sim_groups;
+}
+
 extern "C" {
+
+int kv_sim_groups_for(const kv_config* cfg) {
+    KV_REQUIRE(cfg, KV_EINVAL, "kv_sim_groups_for: NULL");
+    KV_REQUIRE(cfg->sim_groups >= 0 && cfg->sim_groups <= 2, KV_EINVAL, "kv_create: sim_groups %d must be 0 (auto), 1 or 2",
+               cfg->sim_groups);
+    KV_REQUIRE(cfg->sim_groups != 2 || (cfg->sims >= 1 && cfg->slots / 2 > 16), KV_EINVAL,
+               "kv_create: sim_groups 2 needs sims >= 1 and more than 16 slots per group (the network's batch class), "
+               "got sims %d, slots %d", cfg->sims, cfg->slots);
+    return sim_groups_for(cfg);
+}
 
 int kv_create(const kv_config* cfg, kv_engine** out) {
     KV_REQUIRE(cfg && out, KV_EINVAL, "kv_create: NULL argument");
@@ -587,9 +612,12 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     KV_REQUIRE(cfg->reuse_tree == 0 || cfg->sims >= 1, KV_EINVAL,
                "kv_create: reuse_tree carries MCTS subtrees and needs sims >= 1 (sims 0 is the reference move "
                "selection)");
+    const int groups = kv_sim_groups_for(cfg);
+    if (groups < 0) return groups;
     KV_HIP(hipSetDevice(cfg->device));
     kv_engine* e = new kv_engine();
     e->cfg = *cfg;
+    e->groups = groups;
     if (e->cfg.game_id_stride <= 0) e->cfg.game_id_stride = 1;
     if (e->cfg.record_cap <= 0) e->cfg.record_cap = 1 << 20;
     kv::DevCfg& d = e->dc;
@@ -711,6 +739,13 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
         kv::set_error("kv_create: stream");
         return KV_EHIP;
     }
+    if (e->groups == 2 && (hipStreamCreateWithFlags(&e->g_st, hipStreamNonBlocking) != hipSuccess ||
+                           hipEventCreateWithFlags(&e->g_fork, hipEventDisableTiming) != hipSuccess ||
+                           hipEventCreateWithFlags(&e->g_join, hipEventDisableTiming) != hipSuccess)) {
+        kv_destroy(e);
+        kv::set_error("kv_create: group stream");
+        return KV_EHIP;
+    }
     (void)hipMemsetAsync(e->boards, 0, R * 64, e->st);
     (void)hipMemsetAsync(e->ctr, 0, sizeof(kv::Ctr), e->st);
     (void)hipMemsetAsync(e->last_probs, 0, S * 4096 * sizeof(float), e->st);
@@ -734,6 +769,8 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
 int kv_load_weights(kv_engine* e, const float* packed, size_t n_floats) {
     KV_REQUIRE(e, KV_EINVAL, "kv_load_weights: NULL engine");
     KV_HIP(hipStreamSynchronize(e->st));  // the load (and its calibration) runs on the null stream
+    kv::net_view_destroy(e->g_net);  // (idle: the group stream joins the engine stream at every move's end)
+    e->g_net = nullptr;
     int rc = kv_net_load(e->net, packed, n_floats);
     if (rc == KV_OK) e->loaded = true;
     return rc;
@@ -756,15 +793,21 @@ int kv_set_max_moves(kv_engine* e, int max_moves) {
 // the MCTS leaf batch, whose policy is only the leaves' legal moves
 // (kv_net_forward_boards_legal into tree.leaf_logits)
 // `comp`: the leaf batch is the compact active-slot batch (e->mc_*) instead of the slots' rows
-static int eng_eval(kv_engine* e, const int8_t* boards, int rows, bool leaf = false, bool comp = false) {
-    kv_net* net = e->net;
-    hipStream_t st = e->st;
-    float* logits = e->logits;
-    float* values = comp ? e->mc_values : e->values;
+// slot0 / group (the MCTS leaf batch of slots [slot0, slot0 + rows) only): group 1 runs on the group stream with
+// the group's net
+static int eng_eval(kv_engine* e, const int8_t* boards, int rows, bool leaf = false, bool comp = false, int slot0 = 0,
+                    int group = 0) {
+    kv_net* net = group ? e->g_net : e->net;
+    hipStream_t st = group ? e->g_st : e->st;
+    float* logits = e->logits + (size_t)slot0 * 4096;
+    float* values = comp ? e->mc_values : e->values + slot0;
     if (e->dc.eval_mode == KV_EVAL_HASH) {
         int rc = kv::hash_eval(boards, rows, logits, values, st);
         if (rc || !leaf) return rc;
-        return kv::hash_legal(e->tree, rows, st);  // its logits (all 0) in the compact layout
+        kv::Tree ts = e->tree;
+        ts.leaf_cnt += slot0;
+        ts.leaf_logits += (size_t)slot0 * kv::MAXM;
+        return kv::hash_legal(ts, rows, st);  // its logits (all 0) in the compact layout
     }
     if ((size_t)e->n_ev_used + 2 > e->ev.size()) {
         for (int k = 0; k < 2; ++k) {
@@ -776,9 +819,10 @@ static int eng_eval(kv_engine* e, const int8_t* boards, int rows, bool leaf = fa
     kv::net_set_res_events(net, e->ev[e->n_ev_used], e->ev[e->n_ev_used + 1]);
     e->n_ev_used += 2;
     const int rc = leaf ? kv::net_forward_boards_legal_internal(net, boards, rows,
-                                                                comp ? e->mc_moves : e->tree.leaf_moves,
-                                                                comp ? e->mc_cnt : e->tree.leaf_cnt, kv::MAXM,
-                                                                comp ? e->mc_logits : e->tree.leaf_logits,
+                                                                comp ? e->mc_moves : e->tree.leaf_moves + (size_t)slot0 * kv::MAXM,
+                                                                comp ? e->mc_cnt : e->tree.leaf_cnt + slot0, kv::MAXM,
+                                                                comp ? e->mc_logits
+                                                                     : e->tree.leaf_logits + (size_t)slot0 * kv::MAXM,
                                                                 values, st)
                         : kv::net_forward_boards_internal(net, boards, rows, logits, values, st);
     kv::net_set_res_events(net, nullptr, nullptr);
@@ -788,6 +832,45 @@ static int eng_eval(kv_engine* e, const int8_t* boards, int rows, bool leaf = fa
 }
 
 }  // extern "C"
+
+// Sim-steps [k0, k1) of a move's `steps` on the full-slot leaf batch as two slot groups (kv_config.sim_groups):
+// each group's chain -- leaf forward, then backup fused with the next select -- runs on its own stream with its
+// own network workspaces, no host sync and no event between the chains inside the loop. The engine stream (group
+// 0's) has run the root and the first select for every slot; the group stream forks from it here and joins it
+// after the last step. Every board's network row is independent of its batch and every slot's tree and RNG are
+// its own, so the results are those of one group bit for bit. While both chains are in flight each net's R3
+// GEMM sizes its grid for half the CUs (kv_nn.hip gemm_cus).
+static int eng_group_sims(kv_engine* e, int k0, int k1, int steps, bool reuse) {
+    const kv::Tree& t = e->tree;
+    const int S = e->cfg.slots, h = S / 2;
+    int rc = KV_OK;
+    if (k0 >= k1) return KV_OK;
+    if (!e->g_net && (rc = kv::net_view_create(e->net, &e->g_net))) return rc;
+    kv::net_set_cu_share(e->net, 2);
+    kv::net_set_cu_share(e->g_net, 2);
+    KV_HIP(hipEventRecord(e->g_fork, e->st));
+    KV_HIP(hipStreamWaitEvent(e->g_st, e->g_fork, 0));
+    for (int k = k0; k < k1 && !rc; ++k) {
+        for (int g = 0; g < 2 && !rc; ++g) {
+            const int s0 = g ? h : 0, n = g ? S - h : h;
+            hipStream_t st = g ? e->g_st : e->st;
+            if ((rc = eng_eval(e, e->nn_boards + (size_t)s0 * 64, n, true, false, s0, g))) break;
+            rc = k + 1 < steps ? kv::mcts_backup_select(e->dc, t, e->slots, e->boards, e->logits, e->values, e->probs,
+                                                        e->nn_boards, e->ctr, st, s0, n, reuse)
+                               : kv::mcts_backup(e->dc, t, e->slots, e->logits, e->values, e->probs, e->ctr, st, s0, n,
+                                                 reuse);
+        }
+        e->full_rows += S;
+    }
+    kv::net_set_cu_share(e->net, 1);
+    // the join is enqueued on every exit, so that the engine stream never runs ahead of the group stream
+    const hipError_t j0 = hipEventRecord(e->g_join, e->g_st);
+    const hipError_t j1 = hipStreamWaitEvent(e->st, e->g_join, 0);
+    if (rc) return rc;
+    KV_HIP(j0);
+    KV_HIP(j1);
+    return KV_OK;
+}
 
 // One ply's root and sim-steps with kv_config.reuse_tree (DESIGN.md "Carried subtrees in self-play"). The host
 // read every slot's rem with the last counters (0 for a slot that was not active), so it knows for every
@@ -817,8 +900,20 @@ static int eng_reuse_sims(kv_engine* e, int act) {
     int live = act;      // slots with rem > k
     int compacted = -1;  // the live count at the last compaction of this ply (-1: none yet)
     int R = 0;
+    // two slot groups: the leading steps at which every slot is live (the full-slot batch) run as groups; from
+    // the first compact batch on the ply runs as one group
+    int kg = 0;
+    if (e->groups == 2 && act == S) {
+        int lv = act;
+        for (; kg < steps; ++kg) {
+            if (kg > 0) lv -= hist[kg];
+            if (e->mc_slot_of != nullptr && lv < S) break;  // step kg runs the compact batch
+        }
+        if ((rc = eng_group_sims(e, 0, kg, steps, true))) return rc;
+    }
     for (int k = 0; k < steps; ++k) {
         if (k > 0) live -= hist[k];  // the slots whose last step was k - 1
+        if (k < kg) continue;
         const bool comp = e->mc_slot_of != nullptr && live < S;
         if (comp) {
             if (compacted < 0 || compacted - live >= KV_REUSE_COMPACT_STEP) {
@@ -919,7 +1014,9 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
                 if ((rc = kv::mcts_root(e->dc, t, e->slots, e->moves, e->logits, e->values, e->probs, e->np_mt, e->ctr, e->st)))
                     return rc;
                 if ((rc = kv::mcts_select(e->dc, t, e->slots, e->boards, e->nn_boards, e->ctr, e->st, 0, S))) return rc;
-                for (int k = 0; k < e->dc.sims; ++k) {
+                const bool grouped = e->groups == 2 && !comp;  // (a compact batch of the active slots: one group)
+                if (grouped && (rc = eng_group_sims(e, 0, e->dc.sims, e->dc.sims, false))) return rc;
+                for (int k = grouped ? e->dc.sims : 0; k < e->dc.sims; ++k) {
                     if (comp) {
                         hipLaunchKernelGGL(kv::k_gather_leaves, dim3(R), dim3(64), 0, e->st, e->mc_slot_of, e->nn_boards,
                                            t.leaf_moves, t.leaf_cnt, e->mc_boards, e->mc_moves, e->mc_cnt);
@@ -1464,7 +1561,12 @@ void kv_destroy(kv_engine* e) {
     if (e->rem_host) (void)hipHostFree(e->rem_host);
     for (auto x : e->ev) (void)hipEventDestroy(x);
     if (e->copy_done) (void)hipEventDestroy(e->copy_done);
+    if (e->g_st) (void)hipStreamSynchronize(e->g_st);
+    kv::net_view_destroy(e->g_net);
     if (e->net) kv_net_destroy(e->net);
+    if (e->g_fork) (void)hipEventDestroy(e->g_fork);
+    if (e->g_join) (void)hipEventDestroy(e->g_join);
+    if (e->g_st) (void)hipStreamDestroy(e->g_st);
     if (e->st) (void)hipStreamDestroy(e->st);
     delete e;
 }

@@ -678,6 +678,14 @@ struct kv_net {
     int dom_split = 0;  // F(8x8) fp32: points run as 128x128 tiles in the first launch (100: one launch)
     double dom_flop = 0;
     const char* dom_kernel = "conv3x3_kernel<512,32>";  // the launched kernel's name (kv_stats.dom_kernel)
+    // two nets in flight on two streams (kv_dev_net_pair): the share of the CUs the R3 GEMM's grid takes (1: all),
+    // an event per conv recorded after its GEMM, and the net whose events this one's GEMMs wait for
+    int cu_share = 1;
+    hipEvent_t gemm_done[12] = {};
+    kv_net* leader = nullptr;
+    // a view (kv::net_view_create): another net's weights with workspaces and events of its own, for a forward
+    // in flight beside that net's on another stream; it owns only what net_view_destroy frees
+    bool view = false;
 };
 
 // The residual (K 512) GEMM kernel the launchers below chose last on this thread: each launcher names what it
@@ -776,6 +784,13 @@ static int device_cus() {
     if (!cus[dev] && hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         cus[dev] = 0;
     return cus[dev];
+}
+
+// The CUs the R3 GEMM's grid rule counts: the device's, or 1 / share of them for a net that runs beside share - 1
+// others on streams of their own (kv_net::cu_share), so that the GEMMs in flight together fill the chip once
+static int gemm_cus(int share) {
+    const int cus = device_cus();
+    return share > 1 && cus % (8 * share) == 0 ? cus / share : cus;
 }
 
 template <int CIN, int CK, bool RESID>
@@ -1166,7 +1181,7 @@ static int launch_wino88i32_gemm_lagt(const int8_t* V8, const int* ev, const int
 // R3's GEMM with 64-k stages (kv_wino88i.h wino88i32_gemm_r3k64_kernel): 3 x 48 KiB of LDS
 template <int K, int TPW>
 static int launch_wino88i32_gemm_r3k64(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, float* M,
-                                       int rows, int stride, hipStream_t st) {
+                                       int rows, int stride, hipStream_t st, int share = 1) {
     constexpr int bytes = 3 * 4 * 128 * 96 + 2 * TPW * 1024;  // the ring + two groups' tile exponents
     auto kern = kv::wino88i32_gemm_r3k64_kernel<K, TPW>;
     if constexpr (K == 512 && TPW == 5) {  // KV_R3K64_ABL: timing ablations (outputs invalid; A/B tooling only)
@@ -1188,7 +1203,7 @@ static int launch_wino88i32_gemm_r3k64(const int8_t* V8, const int* ev, const in
     // one round: when the TPW-tile groups fill whole rounds of the CUs, one workgroup per CU runs all its rounds'
     // groups back to back, the copy ring running across them (no prologue between them)
     int nwg = tiles / TPW;
-    const int cus = device_cus();
+    const int cus = gemm_cus(share);
     if (r3_one_round() && cus > 0 && cus % 8 == 0 && nwg > cus && nwg % cus == 0) nwg = cus;
     KV_REQUIRE(nwg % 8 == 0 && tiles % (nwg * TPW) == 0, KV_EINVAL, "wino gemm i8 (r3k64): %d tiles, %d workgroups",
                tiles, nwg);
@@ -1202,12 +1217,12 @@ static int launch_wino88i32_gemm_r3k64(const int8_t* V8, const int* ev, const in
 // or fewer tile-times, and t - 1 of t prologues hidden), else 1. C3's 6,400 tiles on 256 CUs: 5 rounds of
 // 5-tile workgroups (25 tile-times either way: 497 vs 511 us); C2's 800: one round of 4-tile workgroups (4
 // tile-times either way: 72 vs 76 us). KV_I8F32_TPW=1: always one tile per workgroup.
-static int i8f32_tiles_per_wg(int rows) {
+static int i8f32_tiles_per_wg(int rows, int share = 1) {
     static const bool off = [] {
         const char* e = getenv("KV_I8F32_TPW");
         return e && e[0] == '1';
     }();
-    const int cus = device_cus();
+    const int cus = gemm_cus(share);
     const int tiles = kv::W88_XI * (rows / 128) * 4;
     if (off || cus <= 0) return 1;
     const int single = (tiles + cus - 1) / cus;
@@ -1456,19 +1471,19 @@ static int launch_wino88i32v_out(kv_net* net, int l, const float* M, int nb, int
 // the fp32 tower's int8-digit GEMM of one conv (K 256: one segment, per-row exponents)
 template <int K>
 static int i8f32_gemm(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, float* M, int rows, int stride,
-                      bool seg, hipStream_t st, bool r3 = false) {
+                      bool seg, hipStream_t st, bool r3 = false, int share = 1) {
     constexpr int D = kv::kI8DigitsF32;
     const I8f32Form& f = i8f32_form();
     if (r3) {  // KV_PATH_WINO88_I8F32R3 (96-byte row lines): the 64-k-stage kernel, tile count as the 4-digit one's
         // (round 6: 357 vs 375 us for the 32-k form on 128-byte lines, forward -3-5 %, profiles/r06_saddr_ab.log)
-        const int tpw = i8f32_tiles_per_wg(rows);
+        const int tpw = i8f32_tiles_per_wg(rows, share);
         if (tpw == 5) {
             note_dom<K>("wino88i32_gemm_r3k64_kernel<512,5>");
-            return launch_wino88i32_gemm_r3k64<K, 5>(V8, ev, U8, eu, M, rows, stride, st);
+            return launch_wino88i32_gemm_r3k64<K, 5>(V8, ev, U8, eu, M, rows, stride, st, share);
         }
         if (tpw == 4) {
             note_dom<K>("wino88i32_gemm_r3k64_kernel<512,4>");
-            return launch_wino88i32_gemm_r3k64<K, 4>(V8, ev, U8, eu, M, rows, stride, st);
+            return launch_wino88i32_gemm_r3k64<K, 4>(V8, ev, U8, eu, M, rows, stride, st, share);
         }
         note_dom<K>("wino88i32_gemm_r3k64_kernel<512,1>");
         return launch_wino88i32_gemm_r3k64<K, 1>(V8, ev, U8, eu, M, rows, stride, st);
@@ -1528,9 +1543,13 @@ static int wino88i32_gemm_layer(kv_net* net, int l, int K, int rows, int stride,
     }
     const int8_t* U = (r3 ? net->U88r3 : net->U88i32) + net->uoff88[l] * D;
     const int* eu = (r3 ? net->eu88r3 : net->eu88i32) + net->euoff[l];
-    rc = K == 256 ? i8f32_gemm<256>(net->V8, net->ev8, U, eu, M, rows, stride, false, st, r3)
-                  : i8f32_gemm<512>(net->V8, net->ev8, U, eu, M, rows, stride, seg, st, r3);
+    // beside a leader (kv_net::leader): this GEMM starts once the leader's GEMM of the same conv is done, so it
+    // runs under the leader's output kernel instead of under its GEMM
+    if (net->leader && net->leader->gemm_done[l]) KV_HIP(hipStreamWaitEvent(st, net->leader->gemm_done[l], 0));
+    rc = K == 256 ? i8f32_gemm<256>(net->V8, net->ev8, U, eu, M, rows, stride, false, st, r3, net->cu_share)
+                  : i8f32_gemm<512>(net->V8, net->ev8, U, eu, M, rows, stride, seg, st, r3, net->cu_share);
     if (rc) return rc;
+    if (net->gemm_done[l]) KV_HIP(hipEventRecord(net->gemm_done[l], st));
     if (mark && net->res_b) KV_HIP(hipEventRecord(net->res_b, st));
     return KV_OK;
 }
@@ -2889,6 +2908,19 @@ int kv_dev_out_phases(int device, int rows, int resid, int r3, unsigned long lon
     return KV_OK;
 }
 
+int kv_dev_net_pair(kv_net* a, kv_net* b, int cu_share, int follow) {
+    KV_REQUIRE(a && b && a != b && cu_share >= 1 && cu_share <= 2, KV_EINVAL, "kv_dev_net_pair: bad argument");
+    KV_REQUIRE(a->device == b->device, KV_EINVAL, "kv_dev_net_pair: the nets are on different devices");
+    KV_HIP(hipSetDevice(a->device));
+    a->cu_share = b->cu_share = cu_share;
+    a->leader = nullptr;
+    b->leader = follow ? a : nullptr;
+    if (follow)
+        for (int l = 1; l < 12; ++l)
+            if (!a->gemm_done[l]) KV_HIP(hipEventCreateWithFlags(&a->gemm_done[l], hipEventDisableTiming));
+    return KV_OK;
+}
+
 int kv_net_set_timing(kv_net* net, int enable) {
     KV_REQUIRE(net, KV_EINVAL, "kv_net_set_timing: NULL");
     net->timing = enable != 0;
@@ -2906,7 +2938,7 @@ int kv_net_last_timing(kv_net* net, float* conv_ms, int* n_conv) {
 }
 
 void kv_net_destroy(kv_net* net) {
-    if (!net) return;
+    if (!net || net->view) return;  // (a view is released by kv::net_view_destroy)
     (void)hipSetDevice(net->device);
     (void)hipFree(net->w);
     (void)hipFree(net->slab);
@@ -2933,6 +2965,8 @@ void kv_net_destroy(kv_net* net) {
     (void)hipFree(net->Mw);
     (void)hipFree(net->V256);
     for (int i = 0; i < 3; ++i) (void)hipEventDestroy(net->ev[i]);
+    for (hipEvent_t x : net->gemm_done)
+        if (x) (void)hipEventDestroy(x);
     delete net;
 }
 
@@ -2940,6 +2974,7 @@ void kv_net_destroy(kv_net* net) {
 
 // internal accessors for the engine (same library)
 namespace kv {
+void net_view_destroy(kv_net* v);
 int net_forward_boards_internal(kv_net* net, const int8_t* boards_dev, int B, float* policy, float* value,
                                 hipStream_t st) {
     return kv_net_forward_boards(net, boards_dev, B, policy, value, (void*)st);
@@ -2948,6 +2983,58 @@ int net_forward_boards_legal_internal(kv_net* net, const int8_t* boards_dev, int
                                       const int* n_moves, int maxm, float* legal, float* value, hipStream_t st) {
     return kv_net_forward_boards_legal(net, boards_dev, B, moves, n_moves, maxm, legal, value, (void*)st);
 }
+// A view of a loaded net: the same device weights (every pointer the load and the calibration built, the paths
+// chosen), its own workspaces (reserved by its first forward, for its own batch), timing events and forward
+// state. Valid until the parent is loaded again, re-prepared or destroyed; destroy the view first.
+int net_view_create(kv_net* parent, kv_net** out) {
+    KV_REQUIRE(parent && parent->loaded && !parent->view && out, KV_EINVAL, "net_view_create: no loaded net");
+    KV_HIP(hipSetDevice(parent->device));
+    kv_net* v = new kv_net(*parent);
+    v->view = true;
+    v->cap = 0;
+    v->x16 = v->X = v->T = v->pfeat = v->slab = nullptr;
+    v->V = v->V256 = v->Mw = nullptr;
+    v->V8 = nullptr;
+    for (size_t& c : v->ws_cap) c = 0;
+    v->ev8 = nullptr;
+    v->evmax8 = nullptr;
+    v->res_a = v->res_b = nullptr;
+    v->legal = {};
+    v->leader = nullptr;
+    for (hipEvent_t& x : v->gemm_done) x = nullptr;
+    for (hipEvent_t& x : v->ev) x = nullptr;
+    for (hipEvent_t& x : v->ev) {
+        if (hipEventCreate(&x) != hipSuccess) {
+            net_view_destroy(v);
+            kv::set_error("net_view_create: hipEventCreate");
+            return KV_EHIP;
+        }
+    }
+    *out = v;
+    return KV_OK;
+}
+void net_view_destroy(kv_net* v) {
+    if (!v || !v->view) return;
+    (void)hipSetDevice(v->device);
+    (void)hipFree(v->slab);
+    (void)hipFree(v->x16);
+    (void)hipFree(v->X);
+    (void)hipFree(v->T);
+    (void)hipFree(v->pfeat);
+    (void)hipFree(v->V8);
+    (void)hipFree(v->ev8);
+    (void)hipFree(v->evmax8);
+    (void)hipFree(v->V);
+    (void)hipFree(v->Mw);
+    (void)hipFree(v->V256);
+    for (hipEvent_t x : v->ev)
+        if (x) (void)hipEventDestroy(x);
+    for (hipEvent_t x : v->gemm_done)
+        if (x) (void)hipEventDestroy(x);
+    delete v;
+}
+// the share of the CUs this net's R3 GEMM grid takes (1: all; 2: half, beside another net's forward in flight)
+void net_set_cu_share(kv_net* net, int share) { net->cu_share = share; }
 int net_set_res_events(kv_net* net, hipEvent_t a, hipEvent_t b) {
     net->res_a = a;
     net->res_b = b;

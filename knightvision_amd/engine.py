@@ -34,13 +34,24 @@ def packed_from(weights) -> np.ndarray:
 from .model import ALGOS, PRECISIONS  # noqa: E402
 
 
+def sim_groups_for(slots: int, sims: int, sim_groups: int = 0) -> int:
+    """The slot groups an engine with these settings runs its sim loop as (kv_sim_groups_for; no GPU needed)."""
+    cfg = _lib.Config(slots=slots, sims=sims, sim_groups=sim_groups)
+    rc = _lib.lib().kv_sim_groups_for(C.byref(cfg))
+    _lib.check(min(rc, 0), "kv_sim_groups_for")
+    return rc
+
+
 class SelfPlayEngine:
     def __init__(self, weights, *, slots=256, n_games=256, seed=42, seed_mode=SEED_PER_GAME, max_moves=None,
                  batch=16, eps=0.25, alpha=0.3, sims=0, c_puct=1.5, eval_mode=EVAL_FAITHFUL, record_cap=None,
                  recycle=True, device=0, game_id_base=0, game_id_stride=1, precision="fp32",
-                 algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False, reuse_tree=False):
+                 algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False, reuse_tree=False,
+                 sim_groups=0):
         """reuse_tree (MCTS, sims >= 1): carry the subtree under the move just played into the next ply
-        (kv_config.reuse_tree); stats() then reports sims_kept / roots_carried."""
+        (kv_config.reuse_tree); stats() then reports sims_kept / roots_carried.
+        sim_groups (MCTS): the slot groups a move's sim loop runs as, each on its own stream (kv_config.sim_groups):
+        0 auto (sim_groups_for), 1 one group, 2 two groups; the results are the same bit for bit."""
         L = _lib.lib()
         keep = 2 if keep_root_moves else (1 if keep_root_visits else 0)  # the move words imply the visits
         if record_cap is None:
@@ -55,7 +66,8 @@ class SelfPlayEngine:
                           max_moves=max_moves if max_moves else 0, batch=batch, eps=eps, alpha=alpha, sims=sims,
                           c_puct=c_puct, eval_mode=eval_mode, record_cap=record_cap, recycle=1 if recycle else 0,
                           precision=PRECISIONS[precision], algo=ALGOS[algo],
-                          tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep, reuse_tree=int(reuse_tree))
+                          tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep, reuse_tree=int(reuse_tree),
+                          sim_groups=int(sim_groups))
         h = C.c_void_p()
         _lib.check(L.kv_create(C.byref(cfg), C.byref(h)), "kv_create")
         self.h = h

@@ -205,6 +205,18 @@ typedef struct {
                              expansion that does not fit raises KV_EOVERFLOW (kv_stats.tree_overflows) */
     int keep_root_visits; /* 1: keep each MCTS move's root visit counts (pi) for kv_root_visits[_device];
                              2: as 1, and also each committed move's root move words for kv_root_moves[_device] */
+    int arena;            /* 0: self-play. 1: a match between two networks (DESIGN.md "Arena"): player A is the net of
+                             kv_load_weights, player B the net of kv_load_weights_b; in the game with global id g A
+                             plays white iff g is even, and a ply's whole search (the root row and every leaf row) runs
+                             on the net of the side to move at the root. Everything else is the self-play search.
+                             kv_game.outcome stays white-perspective. With KV_EVAL_HASH B's rows are A's with the value
+                             negated. Needs sims >= 1, reuse_tree 0 and eval_mode != KV_EVAL_LAZY; sim_groups 2 needs
+                             34 slots; kv_search* is refused. Any other value: KV_EINVAL. (arena and sample_plies stand
+                             before sim_groups: sim_groups and reuse_tree stay the struct's last two fields) */
+    int sample_plies;     /* MCTS move choice (sims >= 1; must be 0 with sims 0). 0: every ply draws random.choices over
+                             the root visit counts. k > 0: plies 0..k-1 draw, from ply k on the move is the first
+                             maximum of the root visit counts in list order and the CPython stream is not advanced.
+                             -1: every ply takes the first maximum. Any other negative value: KV_EINVAL */
     int sim_groups;       /* MCTS self-play: the slot groups a move's sim loop runs as, each group's chain (leaf forward,
                              backup + select) on a stream of its own with its own network workspaces, so that one
                              group's GEMM runs beside the other's output kernels (DESIGN.md "MCTS semantics"). 0: auto
@@ -219,6 +231,11 @@ typedef struct {
 } kv_config;
 
 #define KV_MAXM 320 /* move-list capacity per position */
+/* arena with sim_groups 0 (auto): the two players' chains run on two streams from this many slots (DESIGN.md
+ * "Arena" records the measurement) */
+#ifndef KV_ARENA_TWO_CHAINS_MIN
+#define KV_ARENA_TWO_CHAINS_MIN 256
+#endif
 #define KV_MAX_SIMS 65000 /* MCTS edges keep 16-bit visit counts and child node ids */
 /* reuse_tree: inside a ply the compact leaf batch of the slots still searching is rebuilt at every sim-step
  * whose live count is lower than at the last rebuild by at least this many slots (1: every change; DESIGN.md
@@ -267,6 +284,8 @@ typedef struct {
                                (the rest as 64x128 tiles in a second one; 100: one launch); 0 otherwise */
     char dom_kernel[96];    /* the name of the kernel those launches ran, as the library chose it (template
                                arguments included, e.g. "wino88i32_gemm_lagt_kernel<512,5>") */
+    int64_t arena_rows[2];   /* arena: the leaf-batch rows player A's / player B's net ran, padding included
+                               (arena_rows[0] + arena_rows[1] == leaf_batch_rows); 0, 0 on a self-play engine */
     int64_t sims_kept;      /* reuse_tree: root visits carried into plies, summed over the committed plies
                                (sims + sims_kept == plies x cfg.sims) */
     int64_t roots_carried;  /* reuse_tree: committed plies whose root was a carried tree */
@@ -284,6 +303,11 @@ int kv_sim_groups_for(const kv_config* cfg);
  * calibration (kv_net_calibration), reported by kv_engine_calibration. */
 int kv_load_weights(kv_engine* e, const float* packed, size_t n_floats);
 int kv_engine_calibration(kv_engine* e, kv_calib* out);
+/* Arena (kv_config.arena = 1): player B's weights, prepared with the engine's precision / algo -- under AUTO B gets
+ * a calibration of its own (kv_engine_calibration_b) and may choose another conv path than A's. Both are KV_EINVAL
+ * on an engine created with arena = 0; kv_run on an arena engine needs both weight sets. */
+int kv_load_weights_b(kv_engine* e, const float* packed, size_t n_floats);
+int kv_engine_calibration_b(kv_engine* e, kv_calib* out);
 /* Run ply-steps until every game is finished, or max_steps steps (>= 0), or
  * stop_after_games games have finished in total (>= 0), whichever is first. */
 int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games);

@@ -21,7 +21,8 @@ class Config(C.Structure):
                 ("max_moves", C.c_int), ("batch", C.c_int), ("eps", C.c_double), ("alpha", C.c_double),
                 ("sims", C.c_int), ("c_puct", C.c_float), ("eval_mode", C.c_int), ("record_cap", C.c_int64),
                 ("recycle", C.c_int), ("precision", C.c_int), ("algo", C.c_int), ("tree_edge_cap", C.c_int),
-                ("keep_root_visits", C.c_int), ("sim_groups", C.c_int), ("reuse_tree", C.c_int)]
+                ("keep_root_visits", C.c_int), ("arena", C.c_int), ("sample_plies", C.c_int),
+                ("sim_groups", C.c_int), ("reuse_tree", C.c_int)]
 
 
 class Record(C.Structure):
@@ -40,6 +41,7 @@ class Stats(C.Structure):
                 ("res_conv_launches", C.c_int64), ("step_ms", C.c_double), ("dom_flop", C.c_double),
                 ("dom_algo", C.c_int64), ("tree_overflows", C.c_int64), ("nn_rows_lazy", C.c_int64),
                 ("dom_path", C.c_int64), ("dom_split", C.c_int64), ("dom_kernel", C.c_char * 96),
+                ("arena_rows", C.c_int64 * 2),
                 ("sims_kept", C.c_int64), ("roots_carried", C.c_int64), ("leaf_batch_rows", C.c_int64)]
 
 
@@ -115,6 +117,8 @@ def _declare(L):
         "kv_create": ([P(Config), P(vp)], i),
         "kv_sim_groups_for": ([P(Config)], i),
         "kv_load_weights": ([vp, P(C.c_float), sz], i),
+        "kv_load_weights_b": ([vp, P(C.c_float), sz], i),
+        "kv_engine_calibration_b": ([vp, P(Calib)], i),
         "kv_run": ([vp, i64, i64], i),
         "kv_set_max_moves": ([vp, i], i),
         "kv_records": ([vp, P(Record), sz, P(sz)], i),
@@ -190,7 +194,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_net_forward_boards", "kv_net_forward_boards_legal", "kv_net_set_timing", "kv_net_last_timing", "kv_net_destroy", "kv_net_set_precision", "kv_net_set_algo",
             "kv_net_calibration", "kv_engine_calibration",
             "kv_create", "kv_sim_groups_for",
-            "kv_load_weights", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_sizeof_config", "kv_sizeof_stats", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
+            "kv_load_weights", "kv_load_weights_b", "kv_engine_calibration_b", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_sizeof_config", "kv_sizeof_stats", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
             "kv_search", "kv_sizeof_search_result", "kv_search_advance", "kv_search_continue", "kv_search_tree_size",
             "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm",
             "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_tower_front", "kv_dev_tower_back", "kv_dev_i8gemm_bench",

@@ -65,6 +65,7 @@ struct Ctr {
     int comp_rows;  // KV_EVAL_LAZY above 16 slots: network rows of this step's compact batch
     unsigned long long sims_kept;      // reuse_tree: root visits the committed plies' roots carried in
     unsigned long long roots_carried;  // reuse_tree: committed plies whose root was a carried tree
+    int arena_n[2];  // arena: this ply's active slots whose mover plays on net A / net B (k_arena_split)
 };
 
 struct DevCfg {
@@ -82,6 +83,7 @@ struct DevCfg {
     long long games_cap;  // game-record ring capacity
     int sims;             // 0: reference move selection; >0: PUCT search
     int eval_mode;        // KV_EVAL_*
+    int sample_plies;     // MCTS move choice: 0 every ply drawn, k > 0 first maximum from ply k on, -1 on every ply
 };
 
 __device__ inline Pos slot_pos(const Slot& s, const int8_t* board) {
@@ -403,20 +405,23 @@ __device__ inline unsigned long long commit_move(const DevCfg& cfg, Slot& s, int
 int mcts_root(const DevCfg& cfg, const Tree& t, Slot* slots, const uint16_t* moves, const float* logits,
               const float* values, float* probs_scratch, uint32_t* np_mt, Ctr* ctr, hipStream_t st);
 // select / backup for slots [slot0, slot0 + count); reuse: the kernels of kv_config.reuse_tree, in which a
-// slot whose root holds sims visits takes no descent and no backup
+// slot whose root holds sims visits takes no descent and no backup. list (a device array of `count` slot
+// indices, the arena's per-net lists) != nullptr: the slots list[0 .. count) instead of the contiguous range
 int mcts_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, int8_t* nn_boards,
-                Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse = false);
+                Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse = false, const int* list = nullptr);
 int mcts_backup(const DevCfg& cfg, const Tree& t, const Slot* slots, const float* logits, const float* values,
-                float* probs, Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse = false);
+                float* probs, Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse = false,
+                const int* list = nullptr);
 // backup of one sim-step fused with the next sim-step's select
 int mcts_backup_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, const float* logits,
                        const float* values, float* probs, int8_t* nn_boards, Ctr* ctr, hipStream_t st, int slot0,
-                       int count, bool reuse = false);
+                       int count, bool reuse = false, const int* list = nullptr);
 // reuse_tree: after k_finish, every slot's tree carried (re-rooted on the played edge's child) or dropped
 int mcts_carry(const DevCfg& cfg, const Tree& t, const Slot* slots, Ctr* ctr, hipStream_t st);
 int mcts_choose(const DevCfg& cfg, const Tree& t, Slot* slots, int8_t* boards, uint32_t* py_mt, kv_record* rec,
                 int8_t* last_board, Ctr* ctr, hipStream_t st);
-int hash_eval(const int8_t* boards, int rows, float* logits, float* values, hipStream_t st);
+// negate: the arena's player B under KV_EVAL_HASH (the same rows with the value negated)
+int hash_eval(const int8_t* boards, int rows, float* logits, float* values, hipStream_t st, bool negate = false);
 int hash_legal(const Tree& t, int rows, hipStream_t st);
 
 // position search launches (kv_search.hip), all on `st`; n trees, L leaves in flight per tree

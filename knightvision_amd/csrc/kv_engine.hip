@@ -416,6 +416,76 @@ __global__ __launch_bounds__(64) void k_scatter_leaves(const int* slot_of, const
     for (int j = lane; j < n; j += 64) leaf_logits[(size_t)s * MAXM + j] = cl[(size_t)r * MAXM + j];
 }
 
+// Arena (kv_config.arena, DESIGN.md "Arena"), once per ply after k_movegen: the active slots partitioned by the
+// net of their mover -- player A (list 0) moves in the game with id g when g is even and white is to move, or g is
+// odd and black is; player B (list 1) otherwise. k_compact_active's ballot scan with two ballots per wave, so one
+// pass writes both lists in slot order: list_x[r] = the r-th slot of player x, row_of[i] = slot i's row in its own
+// list or -1, ctr->arena_n = the two counts (read by the host, which sizes the ply's batches from them). pad_to
+// (17 above 16 slots, else 0): a list of 1 .. pad_to - 1 slots is padded to pad_to rows that repeat its first slot,
+// the network's > 16-board class; the lists hold max(slots, 17) entries. cap: the active slots the host counted
+// before k_movegen -- more on the device is a host / device mismatch (error flag 16).
+__global__ __launch_bounds__(1024) void k_arena_split(DevCfg cfg, const Slot* slots, int cap, int pad_to, int* list_a,
+                                                      int* list_b, int* row_of, Ctr* ctr) {
+    __shared__ int wsum[2][16];
+    __shared__ int base[2];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid < 2) base[tid] = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < cfg.slots; c0 += 1024) {
+        const int i = c0 + tid;
+        bool act = false;
+        int x = 0;
+        if (i < cfg.slots) {
+            const Slot s = slots[i];
+            act = s.status == ST_ACTIVE;
+            x = (((s.game_id & 1) == 0) == (s.wtm != 0)) ? 0 : 1;
+        }
+        const unsigned long long bal_a = __ballot(act && x == 0), bal_b = __ballot(act && x == 1);
+        if (lane == 0) {
+            wsum[0][w] = __popcll(bal_a);
+            wsum[1][w] = __popcll(bal_b);
+        }
+        __syncthreads();
+        int off = base[x];
+        for (int k = 0; k < w; ++k) off += wsum[x][k];
+        const int row = off + __popcll((x ? bal_b : bal_a) & ((1ull << lane) - 1));
+        if (i < cfg.slots) row_of[i] = act ? row : -1;
+        if (act) (x ? list_b : list_a)[row] = i;  // row < the list's active slots <= cfg.slots
+        __syncthreads();
+        if (tid < 2)
+            for (int k = 0; k < 16; ++k) base[tid] += wsum[tid][k];
+        __syncthreads();
+    }
+    const int na = base[0], nb = base[1];
+    if (tid == 0) {
+        ctr->arena_n[0] = na;
+        ctr->arena_n[1] = nb;
+        if (na + nb > cap) atomicOr(&ctr->error, 16);
+    }
+    if (na > 0 && na < pad_to)
+        for (int r = na + tid; r < pad_to; r += 1024) list_a[r] = list_a[0];  // padding rows
+    if (nb > 0 && nb < pad_to)
+        for (int r = nb + tid; r < pad_to; r += 1024) list_b[r] = list_b[0];
+}
+
+// arena: the root boards of one player's list -> its compact batch (one wave per row)
+__global__ __launch_bounds__(64) void k_arena_gather_roots(const int* list, const int8_t* boards, int8_t* cb) {
+    const int r = blockIdx.x, lane = threadIdx.x;
+    cb[(size_t)r * 64 + lane] = boards[(size_t)list[r] * 64 + lane];
+}
+
+// arena: the batch's full 4,096-logit rows and values back to the slots' rows (padding rows dropped)
+__global__ __launch_bounds__(256) void k_arena_scatter_roots(const int* list, const int* row_of, const float* cl,
+                                                            const float* cv, float* logits, float* values) {
+    const int r = blockIdx.x, tid = threadIdx.x;
+    const int s = list[r];
+    if (row_of[s] != r) return;
+    if (tid == 0) values[s] = cv[r];
+    const float4* src = (const float4*)(cl + (size_t)r * 4096);
+    float4* dst = (float4*)(logits + (size_t)s * 4096);
+    for (int j = tid; j < 1024; j += 256) dst[j] = src[j];
+}
+
 // the flush rows of sequential mode: boards [slots, 2*slots) = last appended board
 __global__ void k_flush_rows(DevCfg cfg, const Slot* slots, const int8_t* last_board, int8_t* nn_boards) {
     const int i = blockIdx.x, lane = threadIdx.x;
@@ -490,6 +560,21 @@ struct kv_engine {
     hipStream_t g_st = nullptr;
     hipEvent_t g_fork = nullptr, g_join = nullptr;
     kv_net* g_net = nullptr;
+    // arena (kv_config.arena): player B's net, and per player x the slot list of this ply (k_arena_split), the
+    // compact batch of its rows (boards, the leaves' moves / counts / legal logits, values) and its root rows'
+    // full logits; ar_row_of[slot] = the slot's row in its own list. Player A runs on the engine stream, and with
+    // two chains (groups == 2) player B on g_st
+    kv_net* net_b = nullptr;
+    bool loaded_b = false;
+    int* ar_list[2] = {nullptr, nullptr};
+    int* ar_row_of = nullptr;
+    int8_t* ar_boards[2] = {nullptr, nullptr};
+    uint16_t* ar_moves[2] = {nullptr, nullptr};
+    int* ar_cnt[2] = {nullptr, nullptr};
+    float* ar_llogits[2] = {nullptr, nullptr};
+    float* ar_values[2] = {nullptr, nullptr};
+    float* ar_rlogits[2] = {nullptr, nullptr};
+    long long arena_rows[2] = {0, 0};  // kv_stats.arena_rows
     // kv_search: an engine serves either kv_run or kv_search (used: 0 neither yet, 1 kv_run, 2 kv_search)
     int used = 0;
     kv::SearchWs sw = {};
@@ -565,7 +650,10 @@ static int eng_collect_timing(kv_engine* e) {
 
 // kv_config.sim_groups resolved: 0 (auto) is two groups from 2,048 slots in MCTS mode -- each group then keeps
 // the fused R3 stem's 1,024-board floor and the GEMM's one-round grid on half the CUs -- else one
+// An arena (kv_config.arena) runs its two players' chains on two streams from KV_ARENA_TWO_CHAINS_MIN slots
+// (DESIGN.md "Arena" records the measurement the rule comes from)
 static int sim_groups_for(const kv_config* cfg) {
+    if (cfg->sim_groups == 0 && cfg->arena) return cfg->sims > 0 && cfg->slots >= KV_ARENA_TWO_CHAINS_MIN ? 2 : 1;
     if (cfg->sim_groups == 0) return cfg->sims > 0 && cfg->slots >= 2048 ? 2 : 1;
     return cfg->sim_groups;
 }
@@ -612,6 +700,19 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     KV_REQUIRE(cfg->reuse_tree == 0 || cfg->sims >= 1, KV_EINVAL,
                "kv_create: reuse_tree carries MCTS subtrees and needs sims >= 1 (sims 0 is the reference move "
                "selection)");
+    KV_REQUIRE(cfg->arena == 0 || cfg->arena == 1, KV_EINVAL, "kv_create: arena %d must be 0 or 1", cfg->arena);
+    KV_REQUIRE(cfg->arena == 0 || cfg->sims >= 1, KV_EINVAL,
+               "kv_create: arena plays each ply's search on the mover's net and needs sims >= 1 (sims 0 is the "
+               "reference move selection)");
+    KV_REQUIRE(cfg->arena == 0 || cfg->reuse_tree == 0, KV_EINVAL,
+               "kv_create: arena with reuse_tree: a tree grown on one net's rows is not the other player's");
+    KV_REQUIRE(cfg->arena == 0 || cfg->eval_mode != KV_EVAL_LAZY, KV_EINVAL,
+               "kv_create: arena with eval_mode KV_EVAL_LAZY (lazy: reference move selection only)");
+    KV_REQUIRE(cfg->sample_plies >= -1, KV_EINVAL,
+               "kv_create: sample_plies %d must be 0 (every ply drawn), k > 0 (first maximum from ply k on) or -1 "
+               "(first maximum on every ply)", cfg->sample_plies);
+    KV_REQUIRE(cfg->sample_plies == 0 || cfg->sims >= 1, KV_EINVAL,
+               "kv_create: sample_plies %d is the MCTS move choice and must be 0 with sims 0", cfg->sample_plies);
     const int groups = kv_sim_groups_for(cfg);
     if (groups < 0) return groups;
     KV_HIP(hipSetDevice(cfg->device));
@@ -637,6 +738,7 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     d.games_cap = std::max<long long>(1, std::min<long long>(cfg->n_games, 1 << 20));
     d.sims = cfg->sims;
     d.eval_mode = cfg->eval_mode;
+    d.sample_plies = cfg->sample_plies;
     const size_t S = (size_t)cfg->slots, R = (size_t)d.rows;
     int rc = KV_OK;
 #define ALLOC(ptr, bytes)                                   \
@@ -706,6 +808,19 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
             ALLOC(e->mc_values, S * sizeof(float));
         }
         if (cfg->reuse_tree) ALLOC(t.rem, S * sizeof(int));
+        if (cfg->arena) {
+            const size_t RR = std::max<size_t>(S, 17);  // a list of 1-16 slots is padded to 17 rows above 16 slots
+            ALLOC(e->ar_row_of, S * sizeof(int));
+            for (int x = 0; x < 2; ++x) {
+                ALLOC(e->ar_list[x], RR * sizeof(int));
+                ALLOC(e->ar_boards[x], RR * 64);
+                ALLOC(e->ar_moves[x], RR * kv::MAXM * sizeof(uint16_t));
+                ALLOC(e->ar_cnt[x], RR * sizeof(int));
+                ALLOC(e->ar_llogits[x], RR * kv::MAXM * sizeof(float));
+                ALLOC(e->ar_values[x], RR * sizeof(float));
+                ALLOC(e->ar_rlogits[x], RR * 4096 * sizeof(float));
+            }
+        }
         t.ms = e->ms;
         std::vector<float> sq(t.ncap + 2);
         for (int k = 0; k < t.ncap + 2; ++k) sq[k] = (float)sqrt((double)k);
@@ -731,6 +846,12 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     }
     if ((rc = kv_net_create(cfg->device, &e->net)) || (rc = kv_net_set_precision(e->net, cfg->precision)) ||
         (rc = kv_net_set_algo(e->net, cfg->algo))) {
+        kv_destroy(e);
+        return rc;
+    }
+    if (cfg->arena && ((rc = kv_net_create(cfg->device, &e->net_b)) ||
+                       (rc = kv_net_set_precision(e->net_b, cfg->precision)) ||
+                       (rc = kv_net_set_algo(e->net_b, cfg->algo)))) {
         kv_destroy(e);
         return rc;
     }
@@ -776,9 +897,26 @@ int kv_load_weights(kv_engine* e, const float* packed, size_t n_floats) {
     return rc;
 }
 
+int kv_load_weights_b(kv_engine* e, const float* packed, size_t n_floats) {
+    KV_REQUIRE(e, KV_EINVAL, "kv_load_weights_b: NULL engine");
+    KV_REQUIRE(e->cfg.arena == 1, KV_EINVAL,
+               "kv_load_weights_b: the engine was created with arena 0 (self-play has one network)");
+    KV_HIP(hipStreamSynchronize(e->st));  // (the group stream joins the engine stream at every ply's end)
+    int rc = kv_net_load(e->net_b, packed, n_floats);
+    if (rc == KV_OK) e->loaded_b = true;
+    return rc;
+}
+
 int kv_engine_calibration(kv_engine* e, kv_calib* out) {
     KV_REQUIRE(e && out, KV_EINVAL, "kv_engine_calibration: NULL argument");
     return kv_net_calibration(e->net, out);
+}
+
+int kv_engine_calibration_b(kv_engine* e, kv_calib* out) {
+    KV_REQUIRE(e && out, KV_EINVAL, "kv_engine_calibration_b: NULL argument");
+    KV_REQUIRE(e->cfg.arena == 1, KV_EINVAL,
+               "kv_engine_calibration_b: the engine was created with arena 0 (self-play has one network)");
+    return kv_net_calibration(e->net_b, out);
 }
 
 int kv_set_max_moves(kv_engine* e, int max_moves) {
@@ -944,10 +1082,126 @@ static int eng_reuse_sims(kv_engine* e, int act) {
     return KV_OK;
 }
 
+// one network pass of an arena batch: player x's net (or the hash test evaluator, B's value negated) over the R
+// rows of its compact batch on `st` -- the root rows' full logits into ar_rlogits, or the leaves' legal logits
+static int arena_eval(kv_engine* e, int x, int R, bool leaf, hipStream_t st) {
+    kv_net* net = x ? e->net_b : e->net;
+    if (e->dc.eval_mode == KV_EVAL_HASH) {
+        int rc = kv::hash_eval(e->ar_boards[x], R, e->ar_rlogits[x], e->ar_values[x], st, x == 1);
+        if (rc || !leaf) return rc;
+        kv::Tree ts = e->tree;  // k_hash_legal reads the batch's counts and writes its logits through the tree
+        ts.leaf_cnt = e->ar_cnt[x];
+        ts.leaf_logits = e->ar_llogits[x];
+        return kv::hash_legal(ts, R, st);
+    }
+    if ((size_t)e->n_ev_used + 2 > e->ev.size()) {
+        for (int k = 0; k < 2; ++k) {
+            hipEvent_t ev;
+            KV_HIP(hipEventCreate(&ev));
+            e->ev.push_back(ev);
+        }
+    }
+    kv::net_set_res_events(net, e->ev[e->n_ev_used], e->ev[e->n_ev_used + 1]);
+    e->n_ev_used += 2;
+    const int rc = leaf ? kv::net_forward_boards_legal_internal(net, e->ar_boards[x], R, e->ar_moves[x], e->ar_cnt[x],
+                                                                kv::MAXM, e->ar_llogits[x], e->ar_values[x], st)
+                        : kv::net_forward_boards_internal(net, e->ar_boards[x], R, e->ar_rlogits[x], e->ar_values[x],
+                                                          st);
+    kv::net_set_res_events(net, nullptr, nullptr);
+    kv::net_dom_info(net, &e->dom_algo, &e->dom_launches, &e->dom_flop, &e->dom_path, &e->dom_split, &e->dom_kernel);
+    return rc;
+}
+
+// One ply's roots and sim-steps of an arena (kv_config.arena, DESIGN.md "Arena"). k_arena_split partitions the
+// active slots by the net of their mover; the host reads the two counts (the ply's one readback) and sizes each
+// player's batch: n_x rows, padded to 17 above 16 slots. The root rows and every sim-step's leaf rows go through the
+// two lists, gathered per list and scattered back to the slots' rows, so root, select, backup and choose are the
+// self-play kernels. One group: A's batch, then B's, then one backup + select over all slots. Two groups: A's chain
+// (gather, forward, scatter, backup + select over A's list) on the engine stream and B's on the group stream, forked
+// and joined once per ply, both nets sizing their GEMM grids for half the CUs; with one list empty the ply runs as
+// one group. Every slot's tree, leaf row and value are its own and every row is bit-identical inside its batch
+// class, so the two forms give the same bytes.
+static int eng_arena_ply(kv_engine* e, int act) {
+    const kv::Tree& t = e->tree;
+    const int S = e->cfg.slots, sims = e->dc.sims;
+    int rc = KV_OK;
+    hipLaunchKernelGGL(kv::k_arena_split, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, act, S > 16 ? 17 : 0,
+                       e->ar_list[0], e->ar_list[1], e->ar_row_of, e->ctr);
+    KV_HIP(hipGetLastError());
+    KV_HIP(hipMemcpyAsync(e->ctr_host->arena_n, e->ctr->arena_n, 2 * sizeof(int), hipMemcpyDeviceToHost, e->st));
+    KV_HIP(hipStreamSynchronize(e->st));
+    int n[2], R[2];
+    for (int x = 0; x < 2; ++x) {
+        n[x] = e->ctr_host->arena_n[x];
+        R[x] = S > 16 && n[x] > 0 && n[x] < 17 ? 17 : n[x];
+    }
+    KV_REQUIRE(n[0] >= 0 && n[1] >= 0 && n[0] + n[1] <= act, KV_EHIP,
+               "kv_run: arena lists of %d + %d slots, %d active", n[0], n[1], act);
+    for (int x = 0; x < 2; ++x) {  // the root rows, each on its mover's net
+        if (n[x] == 0) continue;
+        hipLaunchKernelGGL(kv::k_arena_gather_roots, dim3(R[x]), dim3(64), 0, e->st, e->ar_list[x], e->boards,
+                           e->ar_boards[x]);
+        KV_HIP(hipGetLastError());
+        if ((rc = arena_eval(e, x, R[x], false, e->st))) return rc;
+        hipLaunchKernelGGL(kv::k_arena_scatter_roots, dim3(R[x]), dim3(256), 0, e->st, e->ar_list[x], e->ar_row_of,
+                           e->ar_rlogits[x], e->ar_values[x], e->logits, e->values);
+        KV_HIP(hipGetLastError());
+    }
+    if ((rc = kv::mcts_root(e->dc, t, e->slots, e->moves, e->logits, e->values, e->probs, e->np_mt, e->ctr, e->st)))
+        return rc;
+    if ((rc = kv::mcts_select(e->dc, t, e->slots, e->boards, e->nn_boards, e->ctr, e->st, 0, S))) return rc;
+    const bool two = e->groups == 2 && n[0] > 0 && n[1] > 0;
+    if (two) {
+        kv::net_set_cu_share(e->net, 2);
+        kv::net_set_cu_share(e->net_b, 2);
+        KV_HIP(hipEventRecord(e->g_fork, e->st));
+        KV_HIP(hipStreamWaitEvent(e->g_st, e->g_fork, 0));
+    }
+    for (int k = 0; k < sims && !rc; ++k) {
+        for (int x = 0; x < 2 && !rc; ++x) {
+            if (n[x] == 0) continue;
+            hipStream_t st = two && x ? e->g_st : e->st;
+            hipLaunchKernelGGL(kv::k_gather_leaves, dim3(R[x]), dim3(64), 0, st, e->ar_list[x], e->nn_boards,
+                               t.leaf_moves, t.leaf_cnt, e->ar_boards[x], e->ar_moves[x], e->ar_cnt[x]);
+            if (hipGetLastError() != hipSuccess) rc = KV_EHIP;
+            if (!rc) rc = arena_eval(e, x, R[x], true, st);
+            if (rc) break;
+            hipLaunchKernelGGL(kv::k_scatter_leaves, dim3(R[x]), dim3(64), 0, st, e->ar_list[x], e->ar_row_of,
+                               e->ar_llogits[x], e->ar_values[x], e->ar_cnt[x], t.leaf_logits, e->values);
+            if (hipGetLastError() != hipSuccess) rc = KV_EHIP;
+            if (rc) break;
+            e->arena_rows[x] += R[x];
+            e->mc_rows += R[x];
+            if (two)
+                rc = k + 1 < sims ? kv::mcts_backup_select(e->dc, t, e->slots, e->boards, e->logits, e->values, e->probs,
+                                                           e->nn_boards, e->ctr, st, 0, n[x], false, e->ar_list[x])
+                                  : kv::mcts_backup(e->dc, t, e->slots, e->logits, e->values, e->probs, e->ctr, st, 0,
+                                                    n[x], false, e->ar_list[x]);
+        }
+        if (!two && !rc)
+            rc = k + 1 < sims ? kv::mcts_backup_select(e->dc, t, e->slots, e->boards, e->logits, e->values, e->probs,
+                                                       e->nn_boards, e->ctr, e->st, 0, S)
+                              : kv::mcts_backup(e->dc, t, e->slots, e->logits, e->values, e->probs, e->ctr, e->st, 0, S);
+    }
+    if (two) {
+        kv::net_set_cu_share(e->net, 1);
+        kv::net_set_cu_share(e->net_b, 1);
+        // the join is enqueued on every exit, so that the engine stream never runs ahead of the group stream
+        const hipError_t j0 = hipEventRecord(e->g_join, e->g_st);
+        const hipError_t j1 = hipStreamWaitEvent(e->st, e->g_join, 0);
+        if (rc) return rc;
+        KV_HIP(j0);
+        KV_HIP(j1);
+    }
+    return rc;
+}
+
 extern "C" {
 
 int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
     KV_REQUIRE(e && e->loaded, KV_EINVAL, "kv_run: engine has no weights");
+    KV_REQUIRE(e->cfg.arena == 0 || e->loaded_b, KV_EINVAL,
+               "kv_run: an arena engine needs both weight sets (kv_load_weights_b has not loaded player B's)");
     KV_REQUIRE(e->used != 2, KV_EINVAL,
                "kv_run: this engine has searched positions (kv_search); an engine serves either kv_run or kv_search");
     e->used = 1;
@@ -990,6 +1244,7 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
             KV_HIP(hipStreamSynchronize(e->st));
             eval_now = e->ctr_host->need_eval != 0;
         }
+        if (e->cfg.arena) eval_now = false;  // the root rows go through the two players' lists (eng_arena_ply)
         if (eval_now && (rc = eng_eval(e, e->boards, e->dc.rows))) return rc;
         if (!mcts) {
             hipLaunchKernelGGL(kv::k_sample, dim3(S), dim3(256), 0, e->st, e->dc, e->slots, e->boards, e->moves,
@@ -1001,7 +1256,9 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
             // fewer active slots than slots (no game left to start): compact leaf batches of the active
             // slots, padded to the network class of the full batch (> 16 boards: at least 17 rows)
             const int act = e->ctr_host->active;
-            if (e->tree.rem) {
+            if (e->cfg.arena) {
+                if ((rc = eng_arena_ply(e, act))) return rc;
+            } else if (e->tree.rem) {
                 if ((rc = eng_reuse_sims(e, act))) return rc;
             } else {
                 const bool comp = e->mc_slot_of != nullptr && act < S;
@@ -1158,6 +1415,8 @@ int kv_search(kv_engine* e, const int8_t* states, int n, const kv_search_params*
                e->cfg.slots);
     KV_REQUIRE(p->leaves >= 1 && p->leaves <= KV_MAX_LEAVES, KV_EINVAL, "kv_search: leaves %d out of range [1, %d]",
                p->leaves, KV_MAX_LEAVES);
+    KV_REQUIRE(e->cfg.arena == 0, KV_EINVAL,
+               "kv_search: an arena engine plays matches (kv_run); a position search has one network");
     KV_REQUIRE(e->cfg.sims >= 1, KV_EINVAL, "kv_search: the engine was created without tree pools (sims 0)");
     KV_REQUIRE(p->sims >= 1 && p->sims <= e->cfg.sims, KV_EINVAL,
                "kv_search: sims %d out of range [1, %d] (the engine's sims size its tree pools)", p->sims,
@@ -1455,6 +1714,8 @@ int kv_stats_get(kv_engine* e, kv_stats* out) {
     out->sims_kept = (int64_t)e->ctr_host->sims_kept;
     out->roots_carried = (int64_t)e->ctr_host->roots_carried;
     out->leaf_batch_rows = e->mc_rows + e->full_rows;
+    out->arena_rows[0] = e->arena_rows[0];
+    out->arena_rows[1] = e->arena_rows[1];
     return KV_OK;
 }
 
@@ -1553,7 +1814,10 @@ void kv_destroy(kv_engine* e) {
                     e->mc_logits, e->mc_values,
                     t.e_V, e->sw.ss, e->sw.lf, e->sw.paths, e->sw.lboards, e->sw.lmoves, e->sw.lcnt, e->sw.llogits,
                     e->sw.lvalues, e->sw.remaining, e->sw.res, e->s_states, e->s_rboards, e->s_rlogits,
-                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves, t.rem};
+                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves, t.rem,
+                    e->ar_row_of, e->ar_list[0], e->ar_list[1], e->ar_boards[0], e->ar_boards[1], e->ar_moves[0],
+                    e->ar_moves[1], e->ar_cnt[0], e->ar_cnt[1], e->ar_llogits[0], e->ar_llogits[1], e->ar_values[0],
+                    e->ar_values[1], e->ar_rlogits[0], e->ar_rlogits[1]};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (e->ctr_host) (void)hipHostFree(e->ctr_host);
@@ -1563,6 +1827,7 @@ void kv_destroy(kv_engine* e) {
     if (e->copy_done) (void)hipEventDestroy(e->copy_done);
     if (e->g_st) (void)hipStreamSynchronize(e->g_st);
     kv::net_view_destroy(e->g_net);
+    if (e->net_b) kv_net_destroy(e->net_b);
     if (e->net) kv_net_destroy(e->net);
     if (e->g_fork) (void)hipEventDestroy(e->g_fork);
     if (e->g_join) (void)hipEventDestroy(e->g_join);

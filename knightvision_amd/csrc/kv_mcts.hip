@@ -24,6 +24,10 @@
 //            caller shrinks it) raises KV_EOVERFLOW.
 //   choose : random.choices over the root visit counts on the CPython stream
 //            (tau = 1), then makeMove / record / termination as the reference.
+//            kv_config.sample_plies: from that ply on (-1: from the first) the first
+//            maximum of the visit counts instead, the CPython stream not advanced.
+// kv_config.arena (kv_engine.hip eng_arena_ply): each ply's root and leaf rows come from the net of the side to
+// move at the root; select / backup then also run over a slot list (one player's slots) instead of a range.
 // With kv_config.reuse_tree the subtree under the move just played is carried into the next ply
 // (k_mcts_carry, DESIGN.md "Carried subtrees in self-play"): the root takes the fresh root's mixed priors, N,
 // W and the children below it stay, and a slot searches only while its root holds fewer than sims visits.
@@ -294,14 +298,15 @@ __device__ inline void mcts_backup_slot(const DevCfg& cfg, const Tree& t, const 
 
 template <bool REUSE>
 __global__ __launch_bounds__(64) void k_mcts_select(DevCfg cfg, Tree t, const Slot* slots, const int8_t* boards,
-                                                    int8_t* nn_boards, Ctr* ctr, int slot0) {
-    mcts_select_slot<REUSE>(cfg, t, slots, boards, nn_boards, ctr, slot0 + blockIdx.x);
+                                                    int8_t* nn_boards, Ctr* ctr, int slot0, const int* list) {
+    mcts_select_slot<REUSE>(cfg, t, slots, boards, nn_boards, ctr, list ? list[blockIdx.x] : slot0 + blockIdx.x);
 }
 
 template <bool REUSE>
 __global__ __launch_bounds__(64) void k_mcts_backup(DevCfg cfg, Tree t, const Slot* slots, const float* logits,
-                                                    const float* values, float* probs, Ctr* ctr, int slot0) {
-    mcts_backup_slot<REUSE>(cfg, t, slots, logits, values, probs, ctr, slot0 + blockIdx.x);
+                                                    const float* values, float* probs, Ctr* ctr, int slot0,
+                                                    const int* list) {
+    mcts_backup_slot<REUSE>(cfg, t, slots, logits, values, probs, ctr, list ? list[blockIdx.x] : slot0 + blockIdx.x);
 }
 
 // backup of sim-step k and select of sim-step k+1 for the same slot in one
@@ -312,8 +317,8 @@ template <bool REUSE>
 __global__ __launch_bounds__(64) void k_mcts_backup_select(DevCfg cfg, Tree t, const Slot* slots,
                                                            const int8_t* boards, const float* logits,
                                                            const float* values, float* probs, int8_t* nn_boards,
-                                                           Ctr* ctr, int slot0) {
-    const int i = slot0 + blockIdx.x;
+                                                           Ctr* ctr, int slot0, const int* list) {
+    const int i = list ? list[blockIdx.x] : slot0 + blockIdx.x;  // (uniform over the workgroup)
     mcts_backup_slot<REUSE>(cfg, t, slots, logits, values, probs, ctr, i);
     __syncthreads();
     mcts_select_slot<REUSE>(cfg, t, slots, boards, nn_boards, ctr, i);
@@ -332,7 +337,17 @@ __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* sl
     const int n = t.node[nb].cnt;
     for (int j = lane; j < n; j += 64) vals[j] = (double)t.e_N[eb + j];
     __syncthreads();
-    if (lane == 0) s_pick = choose_weighted(vals, cum, n, py_mt + (size_t)i * MT_WORDS);
+    if (lane == 0) {
+        if (cfg.sample_plies != 0 && (cfg.sample_plies < 0 || s.ply >= cfg.sample_plies)) {
+            // kv_config.sample_plies: the first maximum of the visit counts in list order, no draw
+            int best = 0;
+            for (int j = 1; j < n; ++j)
+                if (vals[j] > vals[best]) best = j;
+            s_pick = best;
+        } else {
+            s_pick = choose_weighted(vals, cum, n, py_mt + (size_t)i * MT_WORDS);
+        }
+    }
     __syncthreads();
     // the move's counters in one update per slot (one device-scope atomic per
     // slot and sim-step on a shared counter cost ~3.5 us per select / backup)
@@ -410,7 +425,7 @@ __global__ __launch_bounds__(64) void k_mcts_carry(DevCfg cfg, Tree t, const Slo
 // Test evaluator (KV_EVAL_HASH): all logits 0 (uniform priors, exact in
 // float), value = dyadic hash of the 64 board codes. Lets the CPU restatement
 // reproduce every PUCT score bit for bit.
-__global__ void k_hash_eval(const int8_t* boards, int rows, float* logits, float* values) {
+__global__ void k_hash_eval(const int8_t* boards, int rows, float* logits, float* values, int negate) {
     const int r = blockIdx.x, lane = threadIdx.x;
     if (r >= rows) return;
     for (int j = lane; j < 4096; j += 64) logits[(size_t)r * 4096 + j] = 0.f;
@@ -420,7 +435,8 @@ __global__ void k_hash_eval(const int8_t* boards, int rows, float* logits, float
             h ^= (uint8_t)boards[(size_t)r * 64 + q];
             h *= 16777619u;
         }
-        values[r] = (float)((int)(h % 129u) - 64) / 64.0f;
+        const float v = (float)((int)(h % 129u) - 64) / 64.0f;
+        values[r] = negate ? -v : v;  // (the arena's player B)
     }
 }
 
@@ -445,38 +461,38 @@ int mcts_root(const DevCfg& cfg, const Tree& t, Slot* slots, const uint16_t* mov
 }
 
 int mcts_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, int8_t* nn_boards,
-                Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse) {
+                Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse, const int* list) {
     if (reuse)
         hipLaunchKernelGGL(k_mcts_select<true>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, nn_boards, ctr,
-                           slot0);
+                           slot0, list);
     else
         hipLaunchKernelGGL(k_mcts_select<false>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, nn_boards, ctr,
-                           slot0);
+                           slot0, list);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
 
 int mcts_backup(const DevCfg& cfg, const Tree& t, const Slot* slots, const float* logits, const float* values,
-                float* probs, Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse) {
+                float* probs, Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse, const int* list) {
     if (reuse)
         hipLaunchKernelGGL(k_mcts_backup<true>, dim3(count), dim3(64), 0, st, cfg, t, slots, logits, values, probs,
-                           ctr, slot0);
+                           ctr, slot0, list);
     else
         hipLaunchKernelGGL(k_mcts_backup<false>, dim3(count), dim3(64), 0, st, cfg, t, slots, logits, values, probs,
-                           ctr, slot0);
+                           ctr, slot0, list);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
 
 int mcts_backup_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, const float* logits,
                        const float* values, float* probs, int8_t* nn_boards, Ctr* ctr, hipStream_t st, int slot0,
-                       int count, bool reuse) {
+                       int count, bool reuse, const int* list) {
     if (reuse)
         hipLaunchKernelGGL(k_mcts_backup_select<true>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, logits,
-                           values, probs, nn_boards, ctr, slot0);
+                           values, probs, nn_boards, ctr, slot0, list);
     else
         hipLaunchKernelGGL(k_mcts_backup_select<false>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, logits,
-                           values, probs, nn_boards, ctr, slot0);
+                           values, probs, nn_boards, ctr, slot0, list);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
@@ -495,8 +511,8 @@ int mcts_carry(const DevCfg& cfg, const Tree& t, const Slot* slots, Ctr* ctr, hi
     return KV_OK;
 }
 
-int hash_eval(const int8_t* boards, int rows, float* logits, float* values, hipStream_t st) {
-    hipLaunchKernelGGL(k_hash_eval, dim3(rows), dim3(64), 0, st, boards, rows, logits, values);
+int hash_eval(const int8_t* boards, int rows, float* logits, float* values, hipStream_t st, bool negate) {
+    hipLaunchKernelGGL(k_hash_eval, dim3(rows), dim3(64), 0, st, boards, rows, logits, values, negate ? 1 : 0);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }

@@ -34,9 +34,10 @@ def packed_from(weights) -> np.ndarray:
 from .model import ALGOS, PRECISIONS  # noqa: E402
 
 
-def sim_groups_for(slots: int, sims: int, sim_groups: int = 0) -> int:
-    """The slot groups an engine with these settings runs its sim loop as (kv_sim_groups_for; no GPU needed)."""
-    cfg = _lib.Config(slots=slots, sims=sims, sim_groups=sim_groups)
+def sim_groups_for(slots: int, sims: int, sim_groups: int = 0, arena: bool = False) -> int:
+    """The slot groups an engine with these settings runs its sim loop as (kv_sim_groups_for; no GPU needed);
+    arena: a match engine (kv_config.arena), whose groups are its two players' chains."""
+    cfg = _lib.Config(slots=slots, sims=sims, sim_groups=sim_groups, arena=1 if arena else 0)
     rc = _lib.lib().kv_sim_groups_for(C.byref(cfg))
     _lib.check(min(rc, 0), "kv_sim_groups_for")
     return rc
@@ -47,8 +48,14 @@ class SelfPlayEngine:
                  batch=16, eps=0.25, alpha=0.3, sims=0, c_puct=1.5, eval_mode=EVAL_FAITHFUL, record_cap=None,
                  recycle=True, device=0, game_id_base=0, game_id_stride=1, precision="fp32",
                  algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False, reuse_tree=False,
-                 sim_groups=0):
-        """reuse_tree (MCTS, sims >= 1): carry the subtree under the move just played into the next ply
+                 sim_groups=0, opponent=None, sample_plies=0):
+        """opponent (MCTS, sims >= 1): a second weight set makes the engine an arena (kv_config.arena): `weights`
+        is player A, `opponent` player B, A plays white in the games with an even global id, and every ply is
+        searched on the net of the side to move; games()["outcome"] stays white-perspective (arena.summarize
+        attributes it). calibration_b() reports B's conv paths, stats()["arena_rows"] the leaf rows each net ran.
+        sample_plies (MCTS): 0 every ply draws the move from the root visit counts, k > 0 only plies 0..k-1 do and
+        the later ones take the first maximum, -1 every ply takes it (kv_config.sample_plies).
+        reuse_tree (MCTS, sims >= 1): carry the subtree under the move just played into the next ply
         (kv_config.reuse_tree); stats() then reports sims_kept / roots_carried.
         sim_groups (MCTS): the slot groups a move's sim loop runs as, each on its own stream (kv_config.sim_groups):
         0 auto (sim_groups_for), 1 one group, 2 two groups; the results are the same bit for bit."""
@@ -67,7 +74,8 @@ class SelfPlayEngine:
                           c_puct=c_puct, eval_mode=eval_mode, record_cap=record_cap, recycle=1 if recycle else 0,
                           precision=PRECISIONS[precision], algo=ALGOS[algo],
                           tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep, reuse_tree=int(reuse_tree),
-                          sim_groups=int(sim_groups))
+                          sim_groups=int(sim_groups), arena=0 if opponent is None else 1,
+                          sample_plies=int(sample_plies))
         h = C.c_void_p()
         _lib.check(L.kv_create(C.byref(cfg), C.byref(h)), "kv_create")
         self.h = h
@@ -75,6 +83,10 @@ class SelfPlayEngine:
         packed = packed_from(weights)
         _lib.check(L.kv_load_weights(self.h, packed.ctypes.data_as(C.POINTER(C.c_float)), packed.size),
                    "kv_load_weights")
+        if opponent is not None:
+            packed = packed_from(opponent)
+            _lib.check(L.kv_load_weights_b(self.h, packed.ctypes.data_as(C.POINTER(C.c_float)), packed.size),
+                       "kv_load_weights_b")
 
     def run(self, max_steps: int = -1, stop_after_games: int = -1):
         _lib.check(_lib.lib().kv_run(self.h, int(max_steps), int(stop_after_games)), "kv_run")
@@ -185,11 +197,18 @@ class SelfPlayEngine:
         _lib.check(_lib.lib().kv_engine_calibration(self.h, C.byref(c)), "kv_engine_calibration")
         return _lib.calib_dict(c)
 
+    def calibration_b(self) -> dict:
+        """Player B's conv paths and load-time calibration (an arena engine, kv_engine_calibration_b)."""
+        c = _lib.Calib()
+        _lib.check(_lib.lib().kv_engine_calibration_b(self.h, C.byref(c)), "kv_engine_calibration_b")
+        return _lib.calib_dict(c)
+
     def stats(self) -> dict:
         st = _lib.Stats()
         _lib.check(_lib.lib().kv_stats_get(self.h, C.byref(st)), "kv_stats_get")
         out = {k: getattr(st, k) for k, _ in _lib.Stats._fields_}
         out["dom_kernel"] = out["dom_kernel"].decode()
+        out["arena_rows"] = (int(st.arena_rows[0]), int(st.arena_rows[1]))
         return out
 
     def close(self):
@@ -291,6 +310,7 @@ class PositionSearch:
         _lib.check(_lib.lib().kv_stats_get(self.h, C.byref(st)), "kv_stats_get")
         out = {k: getattr(st, k) for k, _ in _lib.Stats._fields_}
         out["dom_kernel"] = out["dom_kernel"].decode()
+        out["arena_rows"] = (0, 0)  # (a position search has one network)
         return out
 
     def close(self):

@@ -30,6 +30,12 @@ dataset tuple carries them as sparse PolicyTargets (policy_targets.py) and
 the update step scores them with the fused HIP loss (train_ops.policy_loss).
 The default, "move", is the reference's loss.
 
+arena_games > 0 (no reference counterpart; the reference evaluates against
+Stockfish here, learn.py:204-206): after an iteration's update the new weights
+play a match against the weights the iteration started from (arena.py,
+kv_config.arena) and the iteration's statistics carry the summary. Reporting
+only: nothing is gated or reverted.
+
 Not reproduced (out of the self-play path): the Stockfish
 evaluation, checkpoints, Telegram and TensorBoard logging.
 """
@@ -95,6 +101,32 @@ def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_m
         if policy_targets:
             return eng.records(), eng.games(), eng.root_visits().astype("uint16"), eng.root_moves()
         return eng.records(), eng.games()
+
+
+def arena_shard(new_weights, old_weights, n_games: int, iteration: int, device, *, sims: int, max_moves=None,
+                slots=256, precision="fp32") -> dict:
+    """A match of `n_games` games between the new weights (player A) and the old ones (player B), the games
+    sharded over the ranks by global id as selfplay_shard shards them (game g of iteration i has the id
+    i * n_games + g; A plays white in the even ids). Every rank returns the same arena.summarize of all the
+    ranks' games (W / D / L summed over ranks), with this rank's engine stats under "stats"."""
+    from . import arena
+    from .engine import GAME_DTYPE
+    dist, rank, world = _dist()
+    dev = torch.device(device)
+    ids = list(range(rank, n_games, world))
+    table, stats = np.zeros(0, dtype=GAME_DTYPE), None
+    if ids:
+        r = arena.play_match(new_weights, old_weights, len(ids), sims=sims, slots=min(slots, len(ids)), seed=SEED,
+                             max_moves=max_moves, device=dev.index or 0, game_id_base=iteration * n_games + rank,
+                             game_id_stride=world, precision=precision)
+        table, stats = r["game_table"], r["stats"]
+    if dist is not None and world > 1:
+        rows = torch.from_numpy(table.view(np.uint8).reshape(-1, GAME_DTYPE.itemsize).copy()).to(dev)
+        rows = gather_rows(rows, dst=None).cpu().numpy()
+        table = np.ascontiguousarray(rows).view(GAME_DTYPE).reshape(-1)
+    out = arena.summarize(table)
+    out["stats"] = stats
+    return out
 
 
 def _max_over_ranks(n: int, dev) -> int:
@@ -257,7 +289,8 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
                        batch_size: int = LEARN_BATCH_SIZE, lr: float = LEARN_LR,
                        accumulate_steps: int = T.ACCUM_STEPS, sims: int = 0, max_moves=None, slots: int = 256,
                        seed: int = 0, games_path: str | None = None, max_samples: int = 10000, log=print,
-                       policy_target: str = "move", reuse_tree: bool = False):
+                       policy_target: str = "move", reuse_tree: bool = False, arena_games: int = 0,
+                       arena_sims: int | None = None):
     """Run the loop (learn.py reinforcement_loop :152-209); returns per-iteration statistics.
     `model` is a knightvision_amd.model.ChessNet (same parameters as ai/model.py) on `device`.
     `games_path`: the reference's JSONL dataset (ChessPGNDataset, :162) the self-play records extend --
@@ -268,9 +301,16 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
     (soft cross-entropy, PolicyTargets + train_ops.policy_loss), which needs sims > 0; the samples of
     `games_path` then carry their one-hot rows.
     `reuse_tree` (sims > 0): self-play carries the searched subtree from ply to ply (kv_config.reuse_tree); the
-    per-iteration statistics then show the carried root visits (sims_kept) beside the new backups (sims)."""
+    per-iteration statistics then show the carried root visits (sims_kept) beside the new backups (sims).
+    `arena_games` > 0 (no reference counterpart): after the iteration's update the new weights (player A) play
+    `arena_games` games against the weights the iteration started from (player B) at `arena_sims` simulations a
+    move (None: `sims`, which must then be > 0), sharded over the ranks by game id; st["arena"] gets
+    arena.summarize of all ranks' games and "updated" (False: the iteration had nothing to train on, the match
+    is the weights against themselves). Reporting only: no gating, no revert. 0: the loop as without it."""
     if policy_target not in ("move", "visits"):
         raise ValueError(f"reinforcement_loop: policy_target {policy_target!r}: 'move' or 'visits'")
+    if arena_games > 0 and (arena_sims if arena_sims is not None else sims) <= 0:
+        raise ValueError("reinforcement_loop: arena_games plays MCTS matches: arena_sims (or sims) must be > 0")
     visits = policy_target == "visits"
     if visits and sims <= 0:
         raise ValueError("reinforcement_loop: policy_target='visits' trains on the search's root visit counts: "
@@ -291,6 +331,7 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
     for it in range(iterations):
         st = {"iteration": it + 1, "policy_target": policy_target}
         n = int(data[0].shape[0]) if data is not None else 0
+        incumbent = packed_from(model).copy() if arena_games > 0 else None  # the weights the iteration starts from
         if n >= 2 * world:  # every rank holds train data (fewer samples: no update this iteration)
             t0 = time.perf_counter()
             tv = train_with_validation(ddp, model, optimizer, data, epochs, batch_size, accumulate_steps, gen,
@@ -302,6 +343,14 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
                       optimizer_steps=ep["optimizer_steps"], val_loss=tv["val_loss"], epochs_run=tv["epochs_run"],
                       train_split=tv["train_split"], val_split=tv["val_split"], lr=tv["lr"])
         model.eval()
+        if arena_games > 0:
+            t0 = time.perf_counter()
+            ar = arena_shard(packed_from(model), incumbent, arena_games, it, dev, max_moves=max_moves, slots=slots,
+                             sims=arena_sims if arena_sims is not None else sims)
+            ar.pop("stats", None)
+            ar["updated"] = n >= 2 * world
+            st["arena"] = ar
+            st["arena_s"] = time.perf_counter() - t0
         t0 = time.perf_counter()
         pi = None
         if visits:

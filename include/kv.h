@@ -205,6 +205,19 @@ typedef struct {
                              expansion that does not fit raises KV_EOVERFLOW (kv_stats.tree_overflows) */
     int keep_root_visits; /* 1: keep each MCTS move's root visit counts (pi) for kv_root_visits[_device];
                              2: as 1, and also each committed move's root move words for kv_root_moves[_device] */
+    int leaves;           /* MCTS self-play and arena (kv_run): descents in flight per game and sim-step (DESIGN.md
+                             "Several leaves per game in self-play"). 0 or 1: one leaf, the k_mcts_* kernels and host
+                             loops. 2..KV_MAX_LEAVES: every ply's search is the sim-step loop of "Position search" on
+                             the self-play root -- up to `leaves` descents per game and step under virtual loss, the
+                             collision rule, backups in descent order -- and a step's network batch is the dense list
+                             of the pending leaves of all games (per player in an arena), so a ply takes between
+                             ceil(sims / leaves) and sims steps. Needs sims >= 1; refused (KV_EINVAL) with
+                             reuse_tree 1, eval_mode KV_EVAL_LAZY or sim_groups 2; sim_groups 0 resolves to 1. The
+                             network batch class of the whole run is that of slots x leaves (<= 16 rows, or above):
+                             in the larger class the root batch and every non-empty leaf batch carry at least 17
+                             rows, short ones padded by repeating their first row. Any other value: KV_EINVAL.
+                             kv_search* keeps its own `leaves` parameter and ignores this one. (leaves stands before
+                             arena: the struct's last four fields stay arena, sample_plies, sim_groups, reuse_tree) */
     int arena;            /* 0: self-play. 1: a match between two networks (DESIGN.md "Arena"): player A is the net of
                              kv_load_weights, player B the net of kv_load_weights_b; in the game with global id g A
                              plays white iff g is even, and a ply's whole search (the root row and every leaf row) runs
@@ -286,6 +299,13 @@ typedef struct {
                                arguments included, e.g. "wino88i32_gemm_lagt_kernel<512,5>") */
     int64_t arena_rows[2];   /* arena: the leaf-batch rows player A's / player B's net ran, padding included
                                (arena_rows[0] + arena_rows[1] == leaf_batch_rows); 0, 0 on a self-play engine */
+    int64_t sim_steps;      /* MCTS sim-steps kv_run ran (select, leaf batch, backup), summed over the ply-steps:
+                               plies' steps x sims with kv_config.leaves <= 1; with more leaves a ply-step runs as many
+                               as its slowest game needs (collisions decide it) */
+    int64_t leaf_rows_pending; /* leaf-batch rows that carried a live game's pending leaf: leaf_batch_rows -
+                               leaf_rows_pending is padding (rows of idle slots, of leaves that ended the game, and the
+                               rows that fill a batch up to its class). Counted per committed ply at its move choice,
+                               so nn_rows == the root rows + leaf_rows_pending when kv_run returns */
     int64_t sims_kept;      /* reuse_tree: root visits carried into plies, summed over the committed plies
                                (sims + sims_kept == plies x cfg.sims) */
     int64_t roots_carried;  /* reuse_tree: committed plies whose root was a carried tree */

@@ -171,6 +171,12 @@ struct SearchLeaf {
     int pad[3];
 };
 
+struct LeafCtr {  // kv_config.leaves > 1: what k_leaves_compact tells the host once per sim-step
+    int pend[2];    // pending leaf rows of the step (arena: of player A's / player B's slots; self-play: [0])
+    int stepping;   // slots that took a descent in the step
+    int remaining;  // of those, the slots whose root still holds fewer than sims backups after the step's
+};
+
 struct SessionSlot {  // per-tree state of a search session (kv_search_advance / kv_search_continue)
     int status;    // SR_* of the current root
     int n_moves;   // its move count
@@ -435,6 +441,12 @@ int search_backup_select(const Tree& t, const SearchWs& w, const Slot* slots, co
 // session: nn_rows and the counters take this call's rows and backups only (kv_search_continue)
 int search_result(const Tree& t, const SearchWs& w, const Slot* slots, Ctr* ctr, int sims, int n, bool session,
                   hipStream_t st);
+// self-play / arena with kv_config.leaves > 1: the sim-step of the position search on the slots' own trees (n slots,
+// L descents per slot). leaves_backup with select: fused with the next step's select
+int leaves_select(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr, int sims,
+                  int n, int L, hipStream_t st);
+int leaves_backup(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr, int sims,
+                  int n, int L, bool select, hipStream_t st);
 // search sessions: play root edge edge[i] in tree i (-1: none), then the per-call reset of a continue
 int search_advance(const Tree& t, const SearchWs& w, Slot* slots, int8_t* boards, uint16_t* moves, int8_t* root_rows,
                    const int* edge, int8_t* states, int n, Ctr* ctr, hipStream_t st);

@@ -468,6 +468,75 @@ __global__ __launch_bounds__(1024) void k_arena_split(DevCfg cfg, const Slot* sl
         for (int r = nb + tid; r < pad_to; r += 1024) list_b[r] = list_b[0];
 }
 
+// kv_config.leaves > 1 (DESIGN.md "Several leaves per game in self-play"), once per sim-step after the select: the
+// dense leaf batch. The select left descent j of slot i at row i * L + j with lcnt[row] = the leaf's moves, 0 for a
+// row without a pending leaf (an idle slot, one whose root holds sims backups, a descent that was dropped or ended
+// the game). One workgroup strides over the slots x L counts, k_arena_split's ballot scan per 1,024 rows: list_x[r]
+// = the r-th pending row of player x in row order (self-play: one list; arena: the player of the slot's mover),
+// row_of[row] = its place in its list or -1, a list of 1 .. pad_to - 1 rows padded to pad_to by repeating its first.
+// lc->pend = the two counts, lc->stepping / remaining = the slots that took a descent / that go on after this
+// step's backups: the host's one readback per step. cap: the entries a list holds (error flag 16 beyond).
+__global__ __launch_bounds__(1024) void k_leaves_compact(DevCfg cfg, const Slot* slots, const SearchSlot* ss,
+                                                         const int* lcnt, int L, int sims, int arena, int cap,
+                                                         int pad_to, int* list_a, int* list_b, int* row_of,
+                                                         LeafCtr* lc, Ctr* ctr) {
+    __shared__ int wsum[2][16];
+    __shared__ int base[2];
+    __shared__ int s_step, s_rem;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid < 2) base[tid] = 0;
+    if (tid == 0) s_step = s_rem = 0;
+    __syncthreads();
+    int step = 0, rem = 0;
+    for (int i = tid; i < cfg.slots; i += 1024) {
+        const SearchSlot q = ss[i];
+        step += q.accepted > 0;
+        rem += q.accepted > 0 && q.done + q.accepted < sims;
+    }
+    if (step) atomicAdd(&s_step, step);
+    if (rem) atomicAdd(&s_rem, rem);
+    const int rows = cfg.slots * L;
+    for (int c0 = 0; c0 < rows; c0 += 1024) {
+        const int r = c0 + tid;
+        bool pend = false;
+        int x = 0;
+        if (r < rows) {
+            pend = lcnt[r] > 0;
+            if (arena && pend) {
+                const Slot s = slots[r / L];
+                x = (((s.game_id & 1) == 0) == (s.wtm != 0)) ? 0 : 1;
+            }
+        }
+        const unsigned long long bal_a = __ballot(pend && x == 0), bal_b = __ballot(pend && x == 1);
+        if (lane == 0) {
+            wsum[0][w] = __popcll(bal_a);
+            wsum[1][w] = __popcll(bal_b);
+        }
+        __syncthreads();
+        int off = base[x];
+        for (int k = 0; k < w; ++k) off += wsum[x][k];
+        const int row = off + __popcll((x ? bal_b : bal_a) & ((1ull << lane) - 1));
+        if (r < rows) row_of[r] = pend && row < cap ? row : -1;
+        if (pend && row < cap) (x ? list_b : list_a)[row] = r;
+        __syncthreads();
+        if (tid < 2)
+            for (int k = 0; k < 16; ++k) base[tid] += wsum[tid][k];
+        __syncthreads();
+    }
+    const int na = base[0], nb = base[1];
+    if (tid == 0) {
+        lc->pend[0] = na;
+        lc->pend[1] = nb;
+        lc->stepping = s_step;
+        lc->remaining = s_rem;
+        if (na > cap || nb > cap) atomicOr(&ctr->error, 16);
+    }
+    if (na > 0 && na < pad_to)
+        for (int r = na + tid; r < pad_to; r += 1024) list_a[r] = list_a[0];  // padding rows
+    if (nb > 0 && nb < pad_to)
+        for (int r = nb + tid; r < pad_to; r += 1024) list_b[r] = list_b[0];
+}
+
 // arena: the root boards of one player's list -> its compact batch (one wave per row)
 __global__ __launch_bounds__(64) void k_arena_gather_roots(const int* list, const int8_t* boards, int8_t* cb) {
     const int r = blockIdx.x, lane = threadIdx.x;
@@ -575,6 +644,27 @@ struct kv_engine {
     float* ar_values[2] = {nullptr, nullptr};
     float* ar_rlogits[2] = {nullptr, nullptr};
     long long arena_rows[2] = {0, 0};  // kv_stats.arena_rows
+    // kv_config.leaves > 1 (leaves: the resolved count, 1 for 0): the per-(slot, descent) workspaces of the step
+    // (lw, rows = slots x leaves), the step's dense batch per player x (self-play: x = 0 only) -- the list of its
+    // pending rows, their boards / moves / counts / legal logits / values -- lf_row_of[row] = the row's place in
+    // its list, and the step's counters on the device and pinned on the host. big: the run's network class is the
+    // > 16-row one (slots x leaves > 16); root_rows: the rows of the self-play root batch (17 for fewer slots in
+    // the big class)
+    int leaves = 1;
+    bool big = false;
+    int root_rows = 0;
+    kv::SearchWs lw = {};
+    int* lf_list[2] = {nullptr, nullptr};
+    int* lf_row_of = nullptr;
+    int8_t* lf_boards[2] = {nullptr, nullptr};
+    uint16_t* lf_moves[2] = {nullptr, nullptr};
+    int* lf_cnt[2] = {nullptr, nullptr};
+    float* lf_logits[2] = {nullptr, nullptr};
+    float* lf_values[2] = {nullptr, nullptr};
+    float* lf_hlogits = nullptr;  // KV_EVAL_HASH: the full rows k_hash_eval writes
+    kv::LeafCtr* lf_ctr = nullptr;
+    kv::LeafCtr* lf_ctr_host = nullptr;  // pinned
+    long long sim_steps = 0;             // kv_stats.sim_steps
     // kv_search: an engine serves either kv_run or kv_search (used: 0 neither yet, 1 kv_run, 2 kv_search)
     int used = 0;
     kv::SearchWs sw = {};
@@ -653,6 +743,7 @@ static int eng_collect_timing(kv_engine* e) {
 // An arena (kv_config.arena) runs its two players' chains on two streams from KV_ARENA_TWO_CHAINS_MIN slots
 // (DESIGN.md "Arena" records the measurement the rule comes from)
 static int sim_groups_for(const kv_config* cfg) {
+    if (cfg->sim_groups == 0 && cfg->leaves > 1) return 1;  // several leaves per game: one chain
     if (cfg->sim_groups == 0 && cfg->arena) return cfg->sims > 0 && cfg->slots >= KV_ARENA_TWO_CHAINS_MIN ? 2 : 1;
     if (cfg->sim_groups == 0) return cfg->sims > 0 && cfg->slots >= 2048 ? 2 : 1;
     return cfg->sim_groups;
@@ -664,6 +755,11 @@ int kv_sim_groups_for(const kv_config* cfg) {
     KV_REQUIRE(cfg, KV_EINVAL, "kv_sim_groups_for: NULL");
     KV_REQUIRE(cfg->sim_groups >= 0 && cfg->sim_groups <= 2, KV_EINVAL, "kv_create: sim_groups %d must be 0 (auto), 1 or 2",
                cfg->sim_groups);
+    KV_REQUIRE(cfg->leaves >= 0 && cfg->leaves <= KV_MAX_LEAVES, KV_EINVAL,
+               "kv_create: leaves %d out of range [0, %d]", cfg->leaves, KV_MAX_LEAVES);
+    KV_REQUIRE(cfg->leaves <= 1 || cfg->sim_groups != 2, KV_EINVAL,
+               "kv_create: leaves %d with sim_groups 2: several leaves per game run as one chain (sim_groups 0 or 1)",
+               cfg->leaves);
     KV_REQUIRE(cfg->sim_groups != 2 || (cfg->sims >= 1 && cfg->slots / 2 > 16), KV_EINVAL,
                "kv_create: sim_groups 2 needs sims >= 1 and more than 16 slots per group (the network's batch class), "
                "got sims %d, slots %d", cfg->sims, cfg->slots);
@@ -687,6 +783,16 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     KV_REQUIRE(cfg->sims >= 0 && cfg->sims <= KV_MAX_SIMS, KV_EINVAL,
                "kv_create: sims %d out of range [0, %d] (16-bit edge visit counts and child ids)", cfg->sims,
                KV_MAX_SIMS);
+    KV_REQUIRE(cfg->leaves >= 0 && cfg->leaves <= KV_MAX_LEAVES, KV_EINVAL,
+               "kv_create: leaves %d out of range [0, %d]", cfg->leaves, KV_MAX_LEAVES);
+    KV_REQUIRE(cfg->leaves <= 1 || cfg->eval_mode != KV_EVAL_LAZY, KV_EINVAL,
+               "kv_create: leaves %d with eval_mode KV_EVAL_LAZY (lazy: reference move selection only)", cfg->leaves);
+    KV_REQUIRE(cfg->leaves <= 1 || cfg->sims >= 1, KV_EINVAL,
+               "kv_create: leaves %d with sims %d: several leaves per game are MCTS descents and need sims >= 1",
+               cfg->leaves, cfg->sims);
+    KV_REQUIRE(cfg->leaves <= 1 || cfg->reuse_tree == 0, KV_EINVAL,
+               "kv_create: leaves %d with reuse_tree 1: a carried tree under virtual loss is not built yet",
+               cfg->leaves);
     KV_REQUIRE(cfg->tree_edge_cap <= 0 || cfg->tree_edge_cap >= kv::MAXM, KV_EINVAL,
                "kv_create: tree_edge_cap %d must be 0 (auto) or >= KV_MAXM (the root's list)", cfg->tree_edge_cap);
     KV_REQUIRE(cfg->sims == 0 || cfg->seed_mode == KV_SEED_PER_GAME, KV_EINVAL,
@@ -739,7 +845,11 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     d.sims = cfg->sims;
     d.eval_mode = cfg->eval_mode;
     d.sample_plies = cfg->sample_plies;
-    const size_t S = (size_t)cfg->slots, R = (size_t)d.rows;
+    e->leaves = std::max(cfg->leaves, 1);
+    e->big = e->leaves > 1 ? (long long)cfg->slots * e->leaves > 16 : cfg->slots > 16;
+    // several leaves in the > 16-row class: a root batch of fewer than 17 slots is padded to 17 rows (empty boards)
+    e->root_rows = e->leaves > 1 && e->big ? std::max(d.rows, 17) : d.rows;
+    const size_t S = (size_t)cfg->slots, R = (size_t)e->root_rows;
     int rc = KV_OK;
 #define ALLOC(ptr, bytes)                                   \
     do {                                                    \
@@ -808,6 +918,33 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
             ALLOC(e->mc_values, S * sizeof(float));
         }
         if (cfg->reuse_tree) ALLOC(t.rem, S * sizeof(int));
+        if (e->leaves > 1) {
+            kv::SearchWs& w = e->lw;
+            const size_t rows = S * (size_t)e->leaves, RR = std::max<size_t>(rows, 17);
+            ALLOC(t.e_V, E * sizeof(uint16_t));
+            ALLOC(w.ss, S * sizeof(kv::SearchSlot));
+            ALLOC(w.lf, rows * sizeof(kv::SearchLeaf));
+            ALLOC(w.paths, rows * (size_t)t.ncap * sizeof(int));
+            ALLOC(w.lboards, rows * 64);
+            ALLOC(w.lmoves, rows * kv::MAXM * sizeof(uint16_t));
+            ALLOC(w.lcnt, rows * sizeof(int));
+            ALLOC(w.llogits, rows * kv::MAXM * sizeof(float));
+            ALLOC(w.lvalues, rows * sizeof(float));
+            ALLOC(e->lf_row_of, rows * sizeof(int));
+            ALLOC(e->lf_ctr, sizeof(kv::LeafCtr));
+            (void)hipMemset(t.e_V, 0, E * sizeof(uint16_t));
+            (void)hipMemset(w.ss, 0, S * sizeof(kv::SearchSlot));
+            (void)hipMemset(w.lcnt, 0, rows * sizeof(int));
+            for (int x = 0; x < (cfg->arena ? 2 : 1); ++x) {
+                ALLOC(e->lf_list[x], RR * sizeof(int));
+                ALLOC(e->lf_boards[x], RR * 64);
+                ALLOC(e->lf_moves[x], RR * kv::MAXM * sizeof(uint16_t));
+                ALLOC(e->lf_cnt[x], RR * sizeof(int));
+                ALLOC(e->lf_logits[x], RR * kv::MAXM * sizeof(float));
+                ALLOC(e->lf_values[x], RR * sizeof(float));
+            }
+            if (cfg->eval_mode == KV_EVAL_HASH) ALLOC(e->lf_hlogits, RR * 4096 * sizeof(float));
+        }
         if (cfg->arena) {
             const size_t RR = std::max<size_t>(S, 17);  // a list of 1-16 slots is padded to 17 rows above 16 slots
             ALLOC(e->ar_row_of, S * sizeof(int));
@@ -834,6 +971,12 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     }
 #undef ALLOC
     if (hipHostMalloc(&e->ctr_host, sizeof(kv::Ctr)) != hipSuccess) {
+        kv_destroy(e);
+        kv::set_error("kv_create: hipHostMalloc failed");
+        return KV_ENOMEM;
+    }
+    if (e->leaves > 1 && hipHostMalloc(&e->lf_ctr_host, sizeof(kv::LeafCtr)) != hipSuccess) {
+        e->lf_ctr_host = nullptr;
         kv_destroy(e);
         kv::set_error("kv_create: hipHostMalloc failed");
         return KV_ENOMEM;
@@ -1032,6 +1175,7 @@ static int eng_reuse_sims(kv_engine* e, int act) {
     }
     KV_REQUIRE(counted == act, KV_EHIP, "kv_run: %d active slots, %d with sim-steps to run (reuse_tree)", act,
                counted);
+    e->sim_steps += steps;
     if ((rc = kv::mcts_root(e->dc, t, e->slots, e->moves, e->logits, e->values, e->probs, e->np_mt, e->ctr, e->st)))
         return rc;
     if ((rc = kv::mcts_select(e->dc, t, e->slots, e->boards, e->nn_boards, e->ctr, e->st, 0, S, true))) return rc;
@@ -1196,6 +1340,102 @@ static int eng_arena_ply(kv_engine* e, int act) {
     return rc;
 }
 
+// one network pass of a dense leaf batch (kv_config.leaves > 1): player x's net (or the hash test evaluator, B's
+// value negated) over the R rows of list x, the leaves' legal logits only
+static int leaves_eval(kv_engine* e, int x, int R) {
+    kv_net* net = x ? e->net_b : e->net;
+    if (e->dc.eval_mode == KV_EVAL_HASH) {
+        int rc = kv::hash_eval(e->lf_boards[x], R, e->lf_hlogits, e->lf_values[x], e->st, x == 1);
+        if (rc) return rc;
+        kv::Tree ts = e->tree;  // k_hash_legal reads the batch's counts and writes its logits through the tree
+        ts.leaf_cnt = e->lf_cnt[x];
+        ts.leaf_logits = e->lf_logits[x];
+        return kv::hash_legal(ts, R, e->st);
+    }
+    if ((size_t)e->n_ev_used + 2 > e->ev.size()) {
+        for (int k = 0; k < 2; ++k) {
+            hipEvent_t ev;
+            KV_HIP(hipEventCreate(&ev));
+            e->ev.push_back(ev);
+        }
+    }
+    kv::net_set_res_events(net, e->ev[e->n_ev_used], e->ev[e->n_ev_used + 1]);
+    e->n_ev_used += 2;
+    const int rc = kv::net_forward_boards_legal_internal(net, e->lf_boards[x], R, e->lf_moves[x], e->lf_cnt[x], kv::MAXM,
+                                                         e->lf_logits[x], e->lf_values[x], e->st);
+    kv::net_set_res_events(net, nullptr, nullptr);
+    kv::net_dom_info(net, &e->dom_algo, &e->dom_launches, &e->dom_flop, &e->dom_path, &e->dom_split, &e->dom_kernel);
+    return rc;
+}
+
+// One ply's roots and sim-steps with kv_config.leaves > 1 (DESIGN.md "Several leaves per game in self-play"),
+// self-play and arena alike, on the engine stream. The roots are the one-leaf engines': the slots' rows (self-play;
+// kv_run has run them) or the two players' lists (eng_arena_ply's root section), then k_mcts_root. A sim-step is
+// select (fused with the backup before it) -> k_leaves_compact -> the host reads the step's counters -> per
+// player gather, forward, scatter of its pending rows, sized from the count and padded to 17 rows in the > 16-row
+// class, none for an empty list -> backup. The ply ends when no slot's root holds fewer than sims backups.
+static int eng_leaves_ply(kv_engine* e, int act) {
+    const kv::Tree& t = e->tree;
+    const kv::SearchWs& w = e->lw;
+    const int S = e->cfg.slots, L = e->leaves, sims = e->dc.sims, rows = S * L, np = e->cfg.arena ? 2 : 1;
+    const int pad_to = e->big ? 17 : 0;
+    int rc = KV_OK;
+    if (e->cfg.arena) {
+        hipLaunchKernelGGL(kv::k_arena_split, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, act, pad_to,
+                           e->ar_list[0], e->ar_list[1], e->ar_row_of, e->ctr);
+        KV_HIP(hipGetLastError());
+        KV_HIP(hipMemcpyAsync(e->ctr_host->arena_n, e->ctr->arena_n, 2 * sizeof(int), hipMemcpyDeviceToHost, e->st));
+        KV_HIP(hipStreamSynchronize(e->st));
+        for (int x = 0; x < 2; ++x) {  // the root rows, each on its mover's net
+            const int n = e->ctr_host->arena_n[x];
+            KV_REQUIRE(n >= 0 && n <= act, KV_EHIP, "kv_run: an arena list of %d slots, %d active", n, act);
+            if (n == 0) continue;
+            const int R = n < pad_to ? pad_to : n;
+            hipLaunchKernelGGL(kv::k_arena_gather_roots, dim3(R), dim3(64), 0, e->st, e->ar_list[x], e->boards,
+                               e->ar_boards[x]);
+            KV_HIP(hipGetLastError());
+            if ((rc = arena_eval(e, x, R, false, e->st))) return rc;
+            hipLaunchKernelGGL(kv::k_arena_scatter_roots, dim3(R), dim3(256), 0, e->st, e->ar_list[x], e->ar_row_of,
+                               e->ar_rlogits[x], e->ar_values[x], e->logits, e->values);
+            KV_HIP(hipGetLastError());
+        }
+    }
+    if ((rc = kv::mcts_root(e->dc, t, e->slots, e->moves, e->logits, e->values, e->probs, e->np_mt, e->ctr, e->st)))
+        return rc;
+    if ((rc = kv::leaves_select(t, w, e->slots, e->boards, e->ctr, sims, S, L, e->st))) return rc;
+    for (int step = 0;; ++step) {
+        // every step backs up at least one descent of every slot that is still searching: at most sims steps
+        KV_REQUIRE(step < sims, KV_EHIP, "kv_run: %d sim-steps without finishing a ply of %d sims", step, sims);
+        hipLaunchKernelGGL(kv::k_leaves_compact, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, w.ss, w.lcnt, L, sims,
+                           e->cfg.arena, std::max(rows, 17), pad_to, e->lf_list[0],
+                           e->lf_list[1] ? e->lf_list[1] : e->lf_list[0], e->lf_row_of, e->lf_ctr, e->ctr);
+        KV_HIP(hipGetLastError());
+        KV_HIP(hipMemcpyAsync(e->lf_ctr_host, e->lf_ctr, sizeof(kv::LeafCtr), hipMemcpyDeviceToHost, e->st));
+        KV_HIP(hipStreamSynchronize(e->st));
+        const kv::LeafCtr lc = *e->lf_ctr_host;
+        if (lc.stepping == 0) break;  // (no slot was left to search when the ply began)
+        e->sim_steps += 1;
+        for (int x = 0; x < np; ++x) {
+            const int n = lc.pend[x];
+            KV_REQUIRE(n >= 0 && n <= rows, KV_EHIP, "kv_run: a leaf batch of %d rows, %d slots x %d leaves", n, S, L);
+            if (n == 0) continue;  // an empty batch runs no forward
+            const int R = n < pad_to ? pad_to : n;
+            hipLaunchKernelGGL(kv::k_gather_leaves, dim3(R), dim3(64), 0, e->st, e->lf_list[x], w.lboards, w.lmoves,
+                               w.lcnt, e->lf_boards[x], e->lf_moves[x], e->lf_cnt[x]);
+            KV_HIP(hipGetLastError());
+            if ((rc = leaves_eval(e, x, R))) return rc;
+            hipLaunchKernelGGL(kv::k_scatter_leaves, dim3(R), dim3(64), 0, e->st, e->lf_list[x], e->lf_row_of,
+                               e->lf_logits[x], e->lf_values[x], e->lf_cnt[x], w.llogits, w.lvalues);
+            KV_HIP(hipGetLastError());
+            e->mc_rows += R;
+            if (e->cfg.arena) e->arena_rows[x] += R;
+        }
+        if ((rc = kv::leaves_backup(t, w, e->slots, e->boards, e->ctr, sims, S, L, lc.remaining > 0, e->st))) return rc;
+        if (lc.remaining == 0) break;
+    }
+    return KV_OK;
+}
+
 extern "C" {
 
 int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
@@ -1245,7 +1485,7 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
             eval_now = e->ctr_host->need_eval != 0;
         }
         if (e->cfg.arena) eval_now = false;  // the root rows go through the two players' lists (eng_arena_ply)
-        if (eval_now && (rc = eng_eval(e, e->boards, e->dc.rows))) return rc;
+        if (eval_now && (rc = eng_eval(e, e->boards, e->root_rows))) return rc;
         if (!mcts) {
             hipLaunchKernelGGL(kv::k_sample, dim3(S), dim3(256), 0, e->st, e->dc, e->slots, e->boards, e->moves,
                                e->logits, e->values, e->last_probs, e->np_mt, e->py_mt, e->rec, e->last_board,
@@ -1256,13 +1496,17 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
             // fewer active slots than slots (no game left to start): compact leaf batches of the active
             // slots, padded to the network class of the full batch (> 16 boards: at least 17 rows)
             const int act = e->ctr_host->active;
-            if (e->cfg.arena) {
+            if (e->leaves > 1) {
+                if ((rc = eng_leaves_ply(e, act))) return rc;
+            } else if (e->cfg.arena) {
                 if ((rc = eng_arena_ply(e, act))) return rc;
+                e->sim_steps += e->dc.sims;
             } else if (e->tree.rem) {
                 if ((rc = eng_reuse_sims(e, act))) return rc;
             } else {
                 const bool comp = e->mc_slot_of != nullptr && act < S;
                 const int R = comp ? (S > 16 ? std::max(act, 17) : act) : S;
+                e->sim_steps += e->dc.sims;
                 if (comp) {
                     hipLaunchKernelGGL(kv::k_compact_active, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, R,
                                        e->mc_slot_of, e->mc_row_of, e->ctr, (const kv::NodeRec*)nullptr, 0, 0);
@@ -1711,6 +1955,9 @@ int kv_stats_get(kv_engine* e, kv_stats* out) {
     snprintf(out->dom_kernel, sizeof(out->dom_kernel), "%s", e->dom_kernel ? e->dom_kernel : "");
     out->tree_overflows = (int64_t)e->ctr_host->tree_overflows;
     out->nn_rows_lazy = e->lazy_rows;
+    out->sim_steps = e->sim_steps;
+    // the MCTS leaf rows k_mcts_choose counted (Ctr::nn_rows; a search engine's are kv_search's own)
+    out->leaf_rows_pending = e->used == 1 && e->dc.sims > 0 ? (int64_t)e->ctr_host->nn_rows : 0;
     out->sims_kept = (int64_t)e->ctr_host->sims_kept;
     out->roots_carried = (int64_t)e->ctr_host->roots_carried;
     out->leaf_batch_rows = e->mc_rows + e->full_rows;
@@ -1817,12 +2064,17 @@ void kv_destroy(kv_engine* e) {
                     e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves, t.rem,
                     e->ar_row_of, e->ar_list[0], e->ar_list[1], e->ar_boards[0], e->ar_boards[1], e->ar_moves[0],
                     e->ar_moves[1], e->ar_cnt[0], e->ar_cnt[1], e->ar_llogits[0], e->ar_llogits[1], e->ar_values[0],
-                    e->ar_values[1], e->ar_rlogits[0], e->ar_rlogits[1]};
+                    e->ar_values[1], e->ar_rlogits[0], e->ar_rlogits[1],
+                    e->lw.ss, e->lw.lf, e->lw.paths, e->lw.lboards, e->lw.lmoves, e->lw.lcnt, e->lw.llogits,
+                    e->lw.lvalues, e->lf_list[0], e->lf_list[1], e->lf_row_of, e->lf_boards[0], e->lf_boards[1],
+                    e->lf_moves[0], e->lf_moves[1], e->lf_cnt[0], e->lf_cnt[1], e->lf_logits[0], e->lf_logits[1],
+                    e->lf_values[0], e->lf_values[1], e->lf_hlogits, e->lf_ctr};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (e->ctr_host) (void)hipHostFree(e->ctr_host);
     if (e->s_rem_host) (void)hipHostFree(e->s_rem_host);
     if (e->rem_host) (void)hipHostFree(e->rem_host);
+    if (e->lf_ctr_host) (void)hipHostFree(e->lf_ctr_host);
     for (auto x : e->ev) (void)hipEventDestroy(x);
     if (e->copy_done) (void)hipEventDestroy(e->copy_done);
     if (e->g_st) (void)hipStreamSynchronize(e->g_st);

@@ -21,6 +21,8 @@
 //            tree's pools in place (or the tree dropped when there is no child)
 //   resume : the per-call reset, then the sim-steps above up to the root's
 //            visit target, carried visits counting
+// kv_run with kv_config.leaves > 1 plays self-play and arena games on the same sim-step (k_leaves_* below, the
+// device functions shared through their SP parameter; the dense leaf batch is kv_engine.hip's).
 // The kernels are templated on HASV: without it (L = 1) no V is read or
 // written and every score is kv_mcts.hip's puct() itself, so the search is
 // the self-play one bit for bit.
@@ -91,8 +93,10 @@ __global__ __launch_bounds__(64) void k_search_load(Tree t, SearchWs w, Slot* sl
     mt_seed_genrand(np_mt + (size_t)i * MT_WORDS, (uint32_t)(seed + (unsigned long long)i));
 }
 
-// one tree's descents of a sim-step, by the 64 threads of its workgroup
-template <bool HASV>
+// one tree's descents of a sim-step, by the 64 threads of its workgroup. SP: the tree is a self-play slot's
+// (kv_config.leaves > 1, k_leaves_* below): it is searched while the slot is active and its root holds fewer than
+// sims backups, and ss.done is written for the step's compaction (sims for a slot that takes no descent)
+template <bool HASV, bool SP = false>
 __device__ inline void search_select_tree(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards,
                                           Ctr* ctr, int sims, int L, int i) {
     __shared__ int8_t root_bd[64];
@@ -103,6 +107,11 @@ __device__ inline void search_select_tree(const Tree& t, const SearchWs& w, cons
     SearchSlot ss = w.ss[i];
     const size_t row0 = (size_t)i * L;
     int accepted = 0;
+    if (SP) {
+        const bool active = slots[i].status == ST_ACTIVE;
+        ss.status = active ? SR_SEARCHED : SR_DRAW;
+        ss.done = active ? t.node[(size_t)i * t.ncap].N - 1 : sims;
+    }
     if (ss.status == SR_SEARCHED && ss.done < sims) {
         const Slot s = slots[i];
         root_bd[lane] = boards[(size_t)i * 64 + lane];
@@ -199,8 +208,10 @@ __device__ inline void search_select_tree(const Tree& t, const SearchWs& w, cons
     }
 }
 
-// one tree's backups of a sim-step, by the 64 threads of its workgroup
-template <bool HASV>
+// one tree's backups of a sim-step, by the 64 threads of its workgroup. SP (a self-play slot): the leaf rows are
+// also counted in MctsSlot::pad[1], which k_mcts_choose adds to Ctr::nn_rows, and the host's counter is the
+// compaction's (k_leaves_compact), not w.remaining
+template <bool HASV, bool SP = false>
 __device__ inline void search_backup_tree(const Tree& t, const SearchWs& w, Ctr* ctr, int sims, int L, int i) {
     __shared__ float pri[MAXM];
     const int lane = threadIdx.x;
@@ -261,6 +272,7 @@ __device__ inline void search_backup_tree(const Tree& t, const SearchWs& w, Ctr*
                 }
             }
             m.pad[0] += 1;
+            if (SP) m.pad[1] += 1;
             ss.leaf_rows += 1;
         }
         // along the path (its edges are distinct): the mover at depth d is the root side flipped d times
@@ -282,7 +294,7 @@ __device__ inline void search_backup_tree(const Tree& t, const SearchWs& w, Ctr*
         ss.vroot = 0;
         w.ss[i] = ss;
         t.ms[i] = m;
-        if (ss.done < sims) atomicAdd(w.remaining, 1);  // the host's one readback per step
+        if (!SP && ss.done < sims) atomicAdd(w.remaining, 1);  // the host's one readback per step
     }
 }
 
@@ -368,6 +380,44 @@ __global__ __launch_bounds__(64) void k_search_result(Tree t, SearchWs w, const 
         atomicAdd(&ctr->sims, (unsigned long long)(ss.done - (session ? se.kept : 0)));
         atomicAdd(&ctr->nn_rows, (unsigned long long)ss.leaf_rows);
     }
+}
+
+// ---- self-play and arena with several leaves per game (kv_config.leaves > 1, DESIGN.md "Several leaves per game
+// in self-play"): the sim-step above on the slots' own trees, after k_mcts_root. One wavefront per slot; the leaf
+// of descent j of slot i is row i * L + j of w. e_V is all 0 between sim-steps (every accepted descent's increments
+// are taken back by its backup, an expansion zeroes its edges'), so the roots k_mcts_root builds need no reset.
+__global__ __launch_bounds__(64) void k_leaves_select(Tree t, SearchWs w, const Slot* slots, const int8_t* boards,
+                                                      Ctr* ctr, int sims, int L) {
+    search_select_tree<true, true>(t, w, slots, boards, ctr, sims, L, blockIdx.x);
+}
+
+__global__ __launch_bounds__(64) void k_leaves_backup(Tree t, SearchWs w, Ctr* ctr, int sims, int L) {
+    search_backup_tree<true, true>(t, w, ctr, sims, L, blockIdx.x);
+}
+
+// backup of sim-step k and select of sim-step k + 1 of the same slot in one launch (k_mcts_backup_select)
+__global__ __launch_bounds__(64) void k_leaves_backup_select(Tree t, SearchWs w, const Slot* slots,
+                                                             const int8_t* boards, Ctr* ctr, int sims, int L) {
+    search_backup_tree<true, true>(t, w, ctr, sims, L, blockIdx.x);
+    __syncthreads();
+    search_select_tree<true, true>(t, w, slots, boards, ctr, sims, L, blockIdx.x);
+}
+
+int leaves_select(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr, int sims,
+                  int n, int L, hipStream_t st) {
+    hipLaunchKernelGGL(k_leaves_select, dim3(n), dim3(64), 0, st, t, w, slots, boards, ctr, sims, L);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
+}
+
+int leaves_backup(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr, int sims,
+                  int n, int L, bool select, hipStream_t st) {
+    if (select)
+        hipLaunchKernelGGL(k_leaves_backup_select, dim3(n), dim3(64), 0, st, t, w, slots, boards, ctr, sims, L);
+    else
+        hipLaunchKernelGGL(k_leaves_backup, dim3(n), dim3(64), 0, st, t, w, ctr, sims, L);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
 }
 
 // ---- search sessions (DESIGN.md "Search sessions") ----

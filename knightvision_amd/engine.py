@@ -34,10 +34,11 @@ def packed_from(weights) -> np.ndarray:
 from .model import ALGOS, PRECISIONS  # noqa: E402
 
 
-def sim_groups_for(slots: int, sims: int, sim_groups: int = 0, arena: bool = False) -> int:
+def sim_groups_for(slots: int, sims: int, sim_groups: int = 0, arena: bool = False, *, leaves: int = 0) -> int:
     """The slot groups an engine with these settings runs its sim loop as (kv_sim_groups_for; no GPU needed);
-    arena: a match engine (kv_config.arena), whose groups are its two players' chains."""
-    cfg = _lib.Config(slots=slots, sims=sims, sim_groups=sim_groups, arena=1 if arena else 0)
+    arena: a match engine (kv_config.arena), whose groups are its two players' chains; leaves > 1
+    (kv_config.leaves): always one group, and sim_groups=2 is refused."""
+    cfg = _lib.Config(slots=slots, sims=sims, sim_groups=sim_groups, arena=1 if arena else 0, leaves=int(leaves))
     rc = _lib.lib().kv_sim_groups_for(C.byref(cfg))
     _lib.check(min(rc, 0), "kv_sim_groups_for")
     return rc
@@ -48,7 +49,7 @@ class SelfPlayEngine:
                  batch=16, eps=0.25, alpha=0.3, sims=0, c_puct=1.5, eval_mode=EVAL_FAITHFUL, record_cap=None,
                  recycle=True, device=0, game_id_base=0, game_id_stride=1, precision="fp32",
                  algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False, reuse_tree=False,
-                 sim_groups=0, opponent=None, sample_plies=0):
+                 sim_groups=0, opponent=None, sample_plies=0, leaves=0):
         """opponent (MCTS, sims >= 1): a second weight set makes the engine an arena (kv_config.arena): `weights`
         is player A, `opponent` player B, A plays white in the games with an even global id, and every ply is
         searched on the net of the side to move; games()["outcome"] stays white-perspective (arena.summarize
@@ -58,7 +59,11 @@ class SelfPlayEngine:
         reuse_tree (MCTS, sims >= 1): carry the subtree under the move just played into the next ply
         (kv_config.reuse_tree); stats() then reports sims_kept / roots_carried.
         sim_groups (MCTS): the slot groups a move's sim loop runs as, each on its own stream (kv_config.sim_groups):
-        0 auto (sim_groups_for), 1 one group, 2 two groups; the results are the same bit for bit."""
+        0 auto (sim_groups_for), 1 one group, 2 two groups; the results are the same bit for bit.
+        leaves (MCTS, self-play and arena; kv_config.leaves): 0 or 1 one descent per game and sim-step; 2..64 that
+        many in flight under virtual loss, a step's network batch being the pending leaves of all games, so a ply
+        takes fewer, larger steps (another search than one leaf's: the visit counts differ). Not with reuse_tree,
+        sim_groups=2 or sims=0. stats() reports sim_steps and leaf_rows_pending."""
         L = _lib.lib()
         keep = 2 if keep_root_moves else (1 if keep_root_visits else 0)  # the move words imply the visits
         if record_cap is None:
@@ -75,7 +80,7 @@ class SelfPlayEngine:
                           precision=PRECISIONS[precision], algo=ALGOS[algo],
                           tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep, reuse_tree=int(reuse_tree),
                           sim_groups=int(sim_groups), arena=0 if opponent is None else 1,
-                          sample_plies=int(sample_plies))
+                          sample_plies=int(sample_plies), leaves=int(leaves))
         h = C.c_void_p()
         _lib.check(L.kv_create(C.byref(cfg), C.byref(h)), "kv_create")
         self.h = h

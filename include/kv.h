@@ -205,6 +205,17 @@ typedef struct {
                              expansion that does not fit raises KV_EOVERFLOW (kv_stats.tree_overflows) */
     int keep_root_visits; /* 1: keep each MCTS move's root visit counts (pi) for kv_root_visits[_device];
                              2: as 1, and also each committed move's root move words for kv_root_moves[_device] */
+    int eval_cache;       /* Evaluation cache (DESIGN.md "Evaluation cache"): entries per network of an exact memo of the
+                             leaf rows in HBM -- one table in self-play, two in an arena -- that kv_run's sim-step
+                             probes before it builds the dense leaf batch and fills after the forward. 0: off (no launch,
+                             argument or byte of the engine changes). Else a power of two in [64, 2^24], with leaves >= 2;
+                             any other value: KV_EINVAL. The key is the row's network inputs (64 board codes, the move
+                             count n, the n move words), compared whole; the payload the n legal logits and the value as
+                             bits, so play is byte for byte the play with it off. Direct-mapped, KV_CACHE_ENTRY_BYTES per
+                             entry; a row of more than KV_CACHE_MAXM moves is never stored. A table lives as long as the
+                             engine; kv_load_weights empties player A's, kv_load_weights_b player B's. kv_search* on
+                             such an engine runs without it. (eval_cache stands before leaves: the struct's last five
+                             fields stay leaves, arena, sample_plies, sim_groups, reuse_tree) */
     int leaves;           /* MCTS self-play and arena (kv_run): descents in flight per game and sim-step (DESIGN.md
                              "Several leaves per game in self-play"). 0 or 1: one leaf, the k_mcts_* kernels and host
                              loops. 2..KV_MAX_LEAVES: every ply's search is the sim-step loop of "Position search" on
@@ -244,6 +255,11 @@ typedef struct {
 } kv_config;
 
 #define KV_MAXM 320 /* move-list capacity per position */
+/* Evaluation cache (kv_config.eval_cache): the moves an entry holds, and an entry's bytes -- 64 board codes, a
+ * 16-byte header (n, the value's bits, 8 reserved), KV_CACHE_MAXM move words, KV_CACHE_MAXM logits' bits = 656,
+ * rounded up to whole 64-byte lines. A table of E entries takes E x (KV_CACHE_ENTRY_BYTES + 4) bytes. */
+#define KV_CACHE_MAXM 96
+#define KV_CACHE_ENTRY_BYTES 704
 /* arena with sim_groups 0 (auto): the two players' chains run on two streams from this many slots (DESIGN.md
  * "Arena" records the measurement) */
 #ifndef KV_ARENA_TWO_CHAINS_MIN
@@ -279,7 +295,8 @@ typedef struct {
     int64_t steps;        /* ply-steps executed */
     int64_t plies;        /* moves committed */
     int64_t games_done;
-    int64_t nn_rows;      /* boards evaluated by the network */
+    int64_t nn_rows;      /* boards evaluated by the network (with kv_config.eval_cache: the rows the search consumed;
+                             nn_rows - cache_hits are the rows the network ran, padding aside) */
     int64_t sims;         /* MCTS backups completed (reuse_tree: a ply adds its new backups, not cfg.sims) */
     int64_t records;
     double res_conv_ms;   /* device time of the measured dominant-kernel launches (HIP events):
@@ -299,6 +316,11 @@ typedef struct {
                                arguments included, e.g. "wino88i32_gemm_lagt_kernel<512,5>") */
     int64_t arena_rows[2];   /* arena: the leaf-batch rows player A's / player B's net ran, padding included
                                (arena_rows[0] + arena_rows[1] == leaf_batch_rows); 0, 0 on a self-play engine */
+    int64_t cache_probes;   /* kv_config.eval_cache: pending leaf rows probed (== leaf_rows_pending when kv_run returns), */
+    int64_t cache_hits;     /* of those the rows an entry answered and the network did not run, */
+    int64_t cache_stores;   /* and the entries written (the sum over both tables of an arena); 0 with the cache off.
+                               (The three stand before sim_steps: the struct's last five fields stay sim_steps,
+                               leaf_rows_pending, sims_kept, roots_carried, leaf_batch_rows) */
     int64_t sim_steps;      /* MCTS sim-steps kv_run ran (select, leaf batch, backup), summed over the ply-steps:
                                plies' steps x sims with kv_config.leaves <= 1; with more leaves a ply-step runs as many
                                as its slowest game needs (collisions decide it) */
@@ -310,7 +332,8 @@ typedef struct {
                                (sims + sims_kept == plies x cfg.sims) */
     int64_t roots_carried;  /* reuse_tree: committed plies whose root was a carried tree */
     int64_t leaf_batch_rows; /* rows of every MCTS leaf batch the network ran in kv_run, padding included, full
-                               and compact batches alike (with reuse_tree 0 too) */
+                               and compact batches alike (with reuse_tree 0 too). With kv_config.eval_cache it and
+                               arena_rows fall with the hits: only the missed rows' (padded) lists run */
 } kv_stats;
 
 typedef struct kv_engine kv_engine;
@@ -446,6 +469,17 @@ int kv_dev_make_move(int device, int8_t* states, const int* index, int n);
  * tail [n] = the stream's next random_sample() after the draws. */
 int kv_dev_dirichlet(int device, const uint64_t* seeds, int n, double alpha, int k, int draws, double* out,
                      int64_t* attempts, double* tail);
+/* The evaluation cache's probe and store kernels (kv_config.eval_cache) on a fresh table of `entries` entries (a
+ * power of two in [64, 2^24]) over n_rows given rows: boards [n_rows][64], moves [n_rows][KV_MAXM] move words,
+ * counts [n_rows] (0 .. KV_MAXM; here a row of 0 moves is probed like any other), and the payload the network
+ * would give: logits [n_rows][KV_MAXM] and values [n_rows] as bits. step_len [n_steps] cuts the rows into
+ * consecutive sim-steps (their sum is n_rows): per step the product's probe over the step's rows, then its store
+ * of the missed ones. hit [n_rows]: 1 where the probe found the row's key; out_logits [n_rows][KV_MAXM] /
+ * out_values [n_rows]: what the probe wrote for a hit (the row's first n logits; everything else stays 0xff
+ * bytes). counters [3] (or NULL): probes, hits, stores as the device counted them. */
+int kv_dev_eval_cache(int device, int entries, const int8_t* boards, const uint16_t* moves, const int* counts,
+                      const uint32_t* logits, const uint32_t* values, int n_rows, const int* step_len, int n_steps,
+                      int32_t* hit, uint32_t* out_logits, uint32_t* out_values, int64_t* counters);
 /* The device's restatement of glibc log (op 0: out = log(x)) / pow (op 1:
  * out = pow(x, y)) (csrc/kv_libm.h, used by the Dirichlet draw), run on the
  * host CPU: the same source compiled for the host, so tests can pin it against

@@ -21,7 +21,7 @@ class Config(C.Structure):
                 ("max_moves", C.c_int), ("batch", C.c_int), ("eps", C.c_double), ("alpha", C.c_double),
                 ("sims", C.c_int), ("c_puct", C.c_float), ("eval_mode", C.c_int), ("record_cap", C.c_int64),
                 ("recycle", C.c_int), ("precision", C.c_int), ("algo", C.c_int), ("tree_edge_cap", C.c_int),
-                ("keep_root_visits", C.c_int), ("leaves", C.c_int), ("arena", C.c_int), ("sample_plies", C.c_int),
+                ("keep_root_visits", C.c_int), ("eval_cache", C.c_int), ("leaves", C.c_int), ("arena", C.c_int), ("sample_plies", C.c_int),
                 ("sim_groups", C.c_int), ("reuse_tree", C.c_int)]
 
 
@@ -41,7 +41,8 @@ class Stats(C.Structure):
                 ("res_conv_launches", C.c_int64), ("step_ms", C.c_double), ("dom_flop", C.c_double),
                 ("dom_algo", C.c_int64), ("tree_overflows", C.c_int64), ("nn_rows_lazy", C.c_int64),
                 ("dom_path", C.c_int64), ("dom_split", C.c_int64), ("dom_kernel", C.c_char * 96),
-                ("arena_rows", C.c_int64 * 2), ("sim_steps", C.c_int64), ("leaf_rows_pending", C.c_int64),
+                ("arena_rows", C.c_int64 * 2), ("cache_probes", C.c_int64), ("cache_hits", C.c_int64),
+                ("cache_stores", C.c_int64), ("sim_steps", C.c_int64), ("leaf_rows_pending", C.c_int64),
                 ("sims_kept", C.c_int64), ("roots_carried", C.c_int64), ("leaf_batch_rows", C.c_int64)]
 
 
@@ -76,6 +77,8 @@ MAXM = 320  # KV_MAXM, move-list capacity per position
 
 MAX_LEAVES = 64  # KV_MAX_LEAVES
 REUSE_COMPACT_STEP = 1  # KV_REUSE_COMPACT_STEP
+CACHE_MAXM = 96  # KV_CACHE_MAXM, the moves an evaluation-cache entry holds
+CACHE_ENTRY_BYTES = 704  # KV_CACHE_ENTRY_BYTES
 
 
 class SearchParams(C.Structure):
@@ -144,6 +147,8 @@ def _declare(L):
         "kv_dev_attacks": ([i, P(C.c_int8), i, P(C.c_uint64)], i),
         "kv_dev_dirichlet": ([i, P(C.c_uint64), i, C.c_double, i, i, P(C.c_double), P(i64), P(C.c_double)], i),
         "kv_dev_py_random": ([i, P(C.c_uint64), i, i, P(C.c_double)], i),
+        "kv_dev_eval_cache": ([i, i, P(C.c_int8), P(C.c_uint16), P(i), P(C.c_uint32), P(C.c_uint32), i, P(i), i,
+                               P(C.c_int32), P(C.c_uint32), P(C.c_uint32), P(i64)], i),
         "kv_host_libm": ([i, P(C.c_double), P(C.c_double), i, P(C.c_double)], i),
         "kv_dev_wino88i": ([i, P(C.c_double), i, P(C.c_double), i, i, i, P(C.c_double), P(C.c_int8), P(i)], i),
         "kv_dev_i8gemm_bench": ([i, i, i, i, i, P(C.c_float), P(C.c_float)], i),
@@ -196,7 +201,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_create", "kv_sim_groups_for",
             "kv_load_weights", "kv_load_weights_b", "kv_engine_calibration_b", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_sizeof_config", "kv_sizeof_stats", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
             "kv_search", "kv_sizeof_search_result", "kv_search_advance", "kv_search_continue", "kv_search_tree_size",
-            "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm",
+            "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm", "kv_dev_eval_cache",
             "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_tower_front", "kv_dev_tower_back", "kv_dev_i8gemm_bench",
             "kv_dev_gemm_clock", "kv_dev_out_phases", "kv_dev_net_pair",
             "kv_pgn_extract", "kv_fen_codes", "kv_san_move_index", "kv_chess_perft", "kv_chess_san", "kv_chess_fen",

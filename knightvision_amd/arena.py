@@ -66,19 +66,22 @@ def elo_of(score: float):
 def play_match(weights_a, weights_b, games: int, *, sims: int, slots: int = 256, seed: int = 0, max_moves=None,
                eps: float = 0.0, alpha: float = 0.3, sample_plies: int = 8, c_puct: float = 1.5, device: int = 0,
                game_id_base: int = 0, game_id_stride: int = 1, precision: str = "fp32", algo: str = "auto",
-               sim_groups: int = 0, eval_mode: int = 0, leaves: int = 0) -> dict:
+               sim_groups: int = 0, eval_mode: int = 0, leaves: int = 0, eval_cache: int = 0) -> dict:
     """`games` games of A (weights_a) against B (weights_b) on one GPU -> summarize() of the game table, plus
     "game_table" (the GAME_DTYPE array, for a caller that sums several ranks) and "stats" (the engine's).
     eps = 0 by default: a match takes no root noise; the openings differ through the first `sample_plies`
     plies, which draw the move from the root visit counts on the per-game seeds (seed + id), after which every
     move is the most visited one (sample_plies=0: every ply drawn, -1: none). leaves > 1: that many descents in
-    flight per game and sim-step (kv_config.leaves), which fills the network batches of a match of few games."""
+    flight per game and sim-step (kv_config.leaves), which fills the network batches of a match of few games.
+    eval_cache (leaves >= 2): entries of each net's exact leaf-row cache (kv_config.eval_cache; 0: off) -- the same
+    games, fewer network rows ("stats" reports cache_hits)."""
     from .engine import SelfPlayEngine
     games = int(games)
     with SelfPlayEngine(weights_a, opponent=weights_b, slots=max(1, min(int(slots), games)), n_games=games, seed=seed,
                         max_moves=max_moves, eps=eps, alpha=alpha, sims=sims, c_puct=c_puct, device=device,
                         game_id_base=game_id_base, game_id_stride=game_id_stride, precision=precision, algo=algo,
-                        sim_groups=sim_groups, sample_plies=sample_plies, eval_mode=eval_mode, leaves=leaves) as eng:
+                        sim_groups=sim_groups, sample_plies=sample_plies, eval_mode=eval_mode, leaves=leaves,
+                        eval_cache=eval_cache) as eng:
         eng.run()
         table = eng.games()
         out = summarize(table)

@@ -177,6 +177,18 @@ struct LeafCtr {  // kv_config.leaves > 1: what k_leaves_compact tells the host 
     int remaining;  // of those, the slots whose root still holds fewer than sims backups after the step's
 };
 
+// kv_config.eval_cache (kv_cache.hip): one network's table -- entries of KV_CACHE_ENTRY_BYTES, a claim word per
+// entry (CACHE_NO_CLAIM between sim-steps), mask = entries - 1 -- and the counters of kv_stats
+struct CacheTab {
+    uint4* ent;
+    int* claim;
+    unsigned mask;
+};
+struct CacheCtr {
+    unsigned long long probes, hits, stores;
+};
+constexpr int CACHE_NO_CLAIM = 0x7f7f7f7f;  // (a byte pattern: hipMemset writes it)
+
 struct SessionSlot {  // per-tree state of a search session (kv_search_advance / kv_search_continue)
     int status;    // SR_* of the current root
     int n_moves;   // its move count
@@ -447,6 +459,15 @@ int leaves_select(const Tree& t, const SearchWs& w, const Slot* slots, const int
                   int n, int L, hipStream_t st);
 int leaves_backup(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr, int sims,
                   int n, int L, bool select, hipStream_t st);
+// kv_config.eval_cache (kv_cache.hip), all on `st`: an empty table; the probe of a sim-step's rows (slots != nullptr:
+// the arena's two tables, row r of slot r / L; a row of fewer than nmin moves is not pending) -> hit[rows], the hits'
+// payload in w.llogits / w.lvalues, the misses' entries in cidx[rows] and claimed; the store of the missed rows from w
+int cache_clear(const CacheTab& t, hipStream_t st);
+int cache_reset_claims(const CacheTab& t, hipStream_t st);  // every claim word back to CACHE_NO_CLAIM, the entries kept
+int cache_probe(const CacheTab& ta, const CacheTab& tb, const Slot* slots, int L, int nmin, const SearchWs& w, int rows,
+                int* hit, int* cidx, CacheCtr* cc, hipStream_t st);
+int cache_store(const CacheTab& ta, const CacheTab& tb, const Slot* slots, int L, int nmin, const SearchWs& w, int rows,
+                const int* hit, const int* cidx, CacheCtr* cc, hipStream_t st);
 // search sessions: play root edge edge[i] in tree i (-1: none), then the per-call reset of a continue
 int search_advance(const Tree& t, const SearchWs& w, Slot* slots, int8_t* boards, uint16_t* moves, int8_t* root_rows,
                    const int* edge, int8_t* states, int n, Ctr* ctr, hipStream_t st);

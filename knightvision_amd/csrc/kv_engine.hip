@@ -475,11 +475,12 @@ __global__ __launch_bounds__(1024) void k_arena_split(DevCfg cfg, const Slot* sl
 // = the r-th pending row of player x in row order (self-play: one list; arena: the player of the slot's mover),
 // row_of[row] = its place in its list or -1, a list of 1 .. pad_to - 1 rows padded to pad_to by repeating its first.
 // lc->pend = the two counts, lc->stepping / remaining = the slots that took a descent / that go on after this
-// step's backups: the host's one readback per step. cap: the entries a list holds (error flag 16 beyond).
+// step's backups: the host's one readback per step. cap: the entries a list holds (error flag 16 beyond). hit
+// (kv_config.eval_cache, else NULL): hit[r] != 0 marks a row the cache answered -- not pending for the lists.
 __global__ __launch_bounds__(1024) void k_leaves_compact(DevCfg cfg, const Slot* slots, const SearchSlot* ss,
                                                          const int* lcnt, int L, int sims, int arena, int cap,
                                                          int pad_to, int* list_a, int* list_b, int* row_of,
-                                                         LeafCtr* lc, Ctr* ctr) {
+                                                         LeafCtr* lc, Ctr* ctr, const int* hit) {
     __shared__ int wsum[2][16];
     __shared__ int base[2];
     __shared__ int s_step, s_rem;
@@ -501,7 +502,7 @@ __global__ __launch_bounds__(1024) void k_leaves_compact(DevCfg cfg, const Slot*
         bool pend = false;
         int x = 0;
         if (r < rows) {
-            pend = lcnt[r] > 0;
+            pend = lcnt[r] > 0 && !(hit && hit[r]);
             if (arena && pend) {
                 const Slot s = slots[r / L];
                 x = (((s.game_id & 1) == 0) == (s.wtm != 0)) ? 0 : 1;
@@ -665,6 +666,15 @@ struct kv_engine {
     kv::LeafCtr* lf_ctr = nullptr;
     kv::LeafCtr* lf_ctr_host = nullptr;  // pinned
     long long sim_steps = 0;             // kv_stats.sim_steps
+    // kv_config.eval_cache (kv_cache.hip): the table of player x's net (self-play: x = 0 only; ent == nullptr: off),
+    // per workspace row the step's hit flag and the entry a miss claimed, and the device's counters
+    kv::CacheTab ec_tab[2] = {{nullptr, nullptr, 0}, {nullptr, nullptr, 0}};
+    int* ec_hit = nullptr;
+    int* ec_idx = nullptr;
+    kv::CacheCtr* ec_ctr = nullptr;
+    // a sim-step's claims are out: set before the probe, cleared once the step's store has handed them back. A step
+    // that returned an error in between leaves it set, and the next ply resets the claim words before it probes
+    bool ec_claims_out = false;
     // kv_search: an engine serves either kv_run or kv_search (used: 0 neither yet, 1 kv_run, 2 kv_search)
     int used = 0;
     kv::SearchWs sw = {};
@@ -793,6 +803,13 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     KV_REQUIRE(cfg->leaves <= 1 || cfg->reuse_tree == 0, KV_EINVAL,
                "kv_create: leaves %d with reuse_tree 1: a carried tree under virtual loss is not built yet",
                cfg->leaves);
+    KV_REQUIRE(cfg->eval_cache == 0 || (cfg->eval_cache >= 64 && cfg->eval_cache <= (1 << 24) &&
+                                        (cfg->eval_cache & (cfg->eval_cache - 1)) == 0),
+               KV_EINVAL, "kv_create: eval_cache %d must be 0 (off) or a power of two in [64, 2^24] (entries per network)",
+               cfg->eval_cache);
+    KV_REQUIRE(cfg->eval_cache == 0 || cfg->leaves >= 2, KV_EINVAL,
+               "kv_create: eval_cache %d with leaves %d: the cache sits in front of the dense leaf batch and needs "
+               "leaves >= 2", cfg->eval_cache, cfg->leaves);
     KV_REQUIRE(cfg->tree_edge_cap <= 0 || cfg->tree_edge_cap >= kv::MAXM, KV_EINVAL,
                "kv_create: tree_edge_cap %d must be 0 (auto) or >= KV_MAXM (the root's list)", cfg->tree_edge_cap);
     KV_REQUIRE(cfg->sims == 0 || cfg->seed_mode == KV_SEED_PER_GAME, KV_EINVAL,
@@ -944,6 +961,23 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
                 ALLOC(e->lf_values[x], RR * sizeof(float));
             }
             if (cfg->eval_mode == KV_EVAL_HASH) ALLOC(e->lf_hlogits, RR * 4096 * sizeof(float));
+            if (cfg->eval_cache) {
+                ALLOC(e->ec_hit, rows * sizeof(int));
+                ALLOC(e->ec_idx, rows * sizeof(int));
+                ALLOC(e->ec_ctr, sizeof(kv::CacheCtr));
+                (void)hipMemset(e->ec_hit, 0, rows * sizeof(int));
+                (void)hipMemset(e->ec_idx, 0, rows * sizeof(int));
+                (void)hipMemset(e->ec_ctr, 0, sizeof(kv::CacheCtr));
+                for (int x = 0; x < (cfg->arena ? 2 : 1); ++x) {
+                    ALLOC(e->ec_tab[x].claim, (size_t)cfg->eval_cache * sizeof(int));
+                    ALLOC(e->ec_tab[x].ent, (size_t)cfg->eval_cache * KV_CACHE_ENTRY_BYTES);
+                    e->ec_tab[x].mask = (unsigned)cfg->eval_cache - 1;
+                    if (kv::cache_clear(e->ec_tab[x], 0) != KV_OK || hipDeviceSynchronize() != hipSuccess) {
+                        kv_destroy(e);
+                        return KV_EHIP;
+                    }
+                }
+            }
         }
         if (cfg->arena) {
             const size_t RR = std::max<size_t>(S, 17);  // a list of 1-16 slots is padded to 17 rows above 16 slots
@@ -1037,6 +1071,11 @@ int kv_load_weights(kv_engine* e, const float* packed, size_t n_floats) {
     e->g_net = nullptr;
     int rc = kv_net_load(e->net, packed, n_floats);
     if (rc == KV_OK) e->loaded = true;
+    if (e->ec_tab[0].ent) {  // kv_config.eval_cache: the rows of the weights before are not this net's
+        const int rc2 = kv::cache_clear(e->ec_tab[0], e->st);
+        if (rc2) return rc2;
+        KV_HIP(hipStreamSynchronize(e->st));
+    }
     return rc;
 }
 
@@ -1047,6 +1086,11 @@ int kv_load_weights_b(kv_engine* e, const float* packed, size_t n_floats) {
     KV_HIP(hipStreamSynchronize(e->st));  // (the group stream joins the engine stream at every ply's end)
     int rc = kv_net_load(e->net_b, packed, n_floats);
     if (rc == KV_OK) e->loaded_b = true;
+    if (e->ec_tab[1].ent) {  // kv_config.eval_cache: player B's table
+        const int rc2 = kv::cache_clear(e->ec_tab[1], e->st);
+        if (rc2) return rc2;
+        KV_HIP(hipStreamSynchronize(e->st));
+    }
     return rc;
 }
 
@@ -1374,12 +1418,23 @@ static int leaves_eval(kv_engine* e, int x, int R) {
 // select (fused with the backup before it) -> k_leaves_compact -> the host reads the step's counters -> per
 // player gather, forward, scatter of its pending rows, sized from the count and padded to 17 rows in the > 16-row
 // class, none for an empty list -> backup. The ply ends when no slot's root holds fewer than sims backups.
+// kv_config.eval_cache adds two launches to a step: the probe before k_leaves_compact (a row the cache answers has
+// its logits and value and stays out of the lists) and, where a list ran, the store of the missed rows after the
+// scatter.
 static int eng_leaves_ply(kv_engine* e, int act) {
     const kv::Tree& t = e->tree;
     const kv::SearchWs& w = e->lw;
     const int S = e->cfg.slots, L = e->leaves, sims = e->dc.sims, rows = S * L, np = e->cfg.arena ? 2 : 1;
     const int pad_to = e->big ? 17 : 0;
+    const bool cache = e->ec_tab[0].ent != nullptr;
+    const kv::CacheTab& ec_b = e->ec_tab[e->cfg.arena ? 1 : 0];
+    const kv::Slot* ec_slots = e->cfg.arena ? e->slots : nullptr;
     int rc = KV_OK;
+    if (cache && e->ec_claims_out) {  // a sim-step failed between its probe and its store
+        for (int x = 0; x < np; ++x)
+            if ((rc = kv::cache_reset_claims(e->ec_tab[x], e->st))) return rc;
+        e->ec_claims_out = false;
+    }
     if (e->cfg.arena) {
         hipLaunchKernelGGL(kv::k_arena_split, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, act, pad_to,
                            e->ar_list[0], e->ar_list[1], e->ar_row_of, e->ctr);
@@ -1406,14 +1461,24 @@ static int eng_leaves_ply(kv_engine* e, int act) {
     for (int step = 0;; ++step) {
         // every step backs up at least one descent of every slot that is still searching: at most sims steps
         KV_REQUIRE(step < sims, KV_EHIP, "kv_run: %d sim-steps without finishing a ply of %d sims", step, sims);
+        if (cache) {
+            e->ec_claims_out = true;
+            if ((rc = kv::cache_probe(e->ec_tab[0], ec_b, ec_slots, L, 1, w, rows, e->ec_hit, e->ec_idx, e->ec_ctr,
+                                      e->st)))
+                return rc;
+        }
         hipLaunchKernelGGL(kv::k_leaves_compact, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, w.ss, w.lcnt, L, sims,
                            e->cfg.arena, std::max(rows, 17), pad_to, e->lf_list[0],
-                           e->lf_list[1] ? e->lf_list[1] : e->lf_list[0], e->lf_row_of, e->lf_ctr, e->ctr);
+                           e->lf_list[1] ? e->lf_list[1] : e->lf_list[0], e->lf_row_of, e->lf_ctr, e->ctr,
+                           cache ? e->ec_hit : nullptr);
         KV_HIP(hipGetLastError());
         KV_HIP(hipMemcpyAsync(e->lf_ctr_host, e->lf_ctr, sizeof(kv::LeafCtr), hipMemcpyDeviceToHost, e->st));
         KV_HIP(hipStreamSynchronize(e->st));
         const kv::LeafCtr lc = *e->lf_ctr_host;
-        if (lc.stepping == 0) break;  // (no slot was left to search when the ply began)
+        if (lc.stepping == 0) {  // (no slot was left to search when the ply began: no row, no claim)
+            e->ec_claims_out = false;
+            break;
+        }
         e->sim_steps += 1;
         for (int x = 0; x < np; ++x) {
             const int n = lc.pend[x];
@@ -1430,6 +1495,10 @@ static int eng_leaves_ply(kv_engine* e, int act) {
             e->mc_rows += R;
             if (e->cfg.arena) e->arena_rows[x] += R;
         }
+        if (cache && lc.pend[0] + (np > 1 ? lc.pend[1] : 0) > 0 &&
+            (rc = kv::cache_store(e->ec_tab[0], ec_b, ec_slots, L, 1, w, rows, e->ec_hit, e->ec_idx, e->ec_ctr, e->st)))
+            return rc;
+        e->ec_claims_out = false;  // (a step without a miss took none)
         if ((rc = kv::leaves_backup(t, w, e->slots, e->boards, e->ctr, sims, S, L, lc.remaining > 0, e->st))) return rc;
         if (lc.remaining == 0) break;
     }
@@ -1963,6 +2032,11 @@ int kv_stats_get(kv_engine* e, kv_stats* out) {
     out->leaf_batch_rows = e->mc_rows + e->full_rows;
     out->arena_rows[0] = e->arena_rows[0];
     out->arena_rows[1] = e->arena_rows[1];
+    kv::CacheCtr cc = {0, 0, 0};
+    if (e->ec_ctr) KV_HIP(hipMemcpy(&cc, e->ec_ctr, sizeof(cc), hipMemcpyDeviceToHost));  // (eng_counters has synced)
+    out->cache_probes = (int64_t)cc.probes;
+    out->cache_hits = (int64_t)cc.hits;
+    out->cache_stores = (int64_t)cc.stores;
     return KV_OK;
 }
 
@@ -2068,7 +2142,9 @@ void kv_destroy(kv_engine* e) {
                     e->lw.ss, e->lw.lf, e->lw.paths, e->lw.lboards, e->lw.lmoves, e->lw.lcnt, e->lw.llogits,
                     e->lw.lvalues, e->lf_list[0], e->lf_list[1], e->lf_row_of, e->lf_boards[0], e->lf_boards[1],
                     e->lf_moves[0], e->lf_moves[1], e->lf_cnt[0], e->lf_cnt[1], e->lf_logits[0], e->lf_logits[1],
-                    e->lf_values[0], e->lf_values[1], e->lf_hlogits, e->lf_ctr};
+                    e->lf_values[0], e->lf_values[1], e->lf_hlogits, e->lf_ctr,
+                    e->ec_tab[0].ent, e->ec_tab[0].claim, e->ec_tab[1].ent, e->ec_tab[1].claim, e->ec_hit, e->ec_idx,
+                    e->ec_ctr};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (e->ctr_host) (void)hipHostFree(e->ctr_host);

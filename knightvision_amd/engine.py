@@ -49,7 +49,7 @@ class SelfPlayEngine:
                  batch=16, eps=0.25, alpha=0.3, sims=0, c_puct=1.5, eval_mode=EVAL_FAITHFUL, record_cap=None,
                  recycle=True, device=0, game_id_base=0, game_id_stride=1, precision="fp32",
                  algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False, reuse_tree=False,
-                 sim_groups=0, opponent=None, sample_plies=0, leaves=0):
+                 sim_groups=0, opponent=None, sample_plies=0, leaves=0, eval_cache=0):
         """opponent (MCTS, sims >= 1): a second weight set makes the engine an arena (kv_config.arena): `weights`
         is player A, `opponent` player B, A plays white in the games with an even global id, and every ply is
         searched on the net of the side to move; games()["outcome"] stays white-perspective (arena.summarize
@@ -63,7 +63,12 @@ class SelfPlayEngine:
         leaves (MCTS, self-play and arena; kv_config.leaves): 0 or 1 one descent per game and sim-step; 2..64 that
         many in flight under virtual loss, a step's network batch being the pending leaves of all games, so a ply
         takes fewer, larger steps (another search than one leaf's: the visit counts differ). Not with reuse_tree,
-        sim_groups=2 or sims=0. stats() reports sim_steps and leaf_rows_pending."""
+        sim_groups=2 or sims=0. stats() reports sim_steps and leaf_rows_pending.
+        eval_cache (leaves >= 2; kv_config.eval_cache): entries per network of an exact cache of the leaf rows in HBM,
+        a power of two in [64, 2^24], 0 off: a leaf whose board and move list were evaluated before takes the stored
+        logits and value and leaves the step's network batch. Play is byte for byte the play without it; stats()
+        reports cache_probes / cache_hits / cache_stores, and nn_rows - cache_hits rows ran on the network.
+        load_weights / load_opponent empty the table of the net they replace."""
         L = _lib.lib()
         keep = 2 if keep_root_moves else (1 if keep_root_visits else 0)  # the move words imply the visits
         if record_cap is None:
@@ -80,18 +85,26 @@ class SelfPlayEngine:
                           precision=PRECISIONS[precision], algo=ALGOS[algo],
                           tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep, reuse_tree=int(reuse_tree),
                           sim_groups=int(sim_groups), arena=0 if opponent is None else 1,
-                          sample_plies=int(sample_plies), leaves=int(leaves))
+                          sample_plies=int(sample_plies), leaves=int(leaves), eval_cache=int(eval_cache))
         h = C.c_void_p()
         _lib.check(L.kv_create(C.byref(cfg), C.byref(h)), "kv_create")
         self.h = h
         self.cfg = cfg
-        packed = packed_from(weights)
-        _lib.check(L.kv_load_weights(self.h, packed.ctypes.data_as(C.POINTER(C.c_float)), packed.size),
-                   "kv_load_weights")
+        self.load_weights(weights)
         if opponent is not None:
-            packed = packed_from(opponent)
-            _lib.check(L.kv_load_weights_b(self.h, packed.ctypes.data_as(C.POINTER(C.c_float)), packed.size),
-                       "kv_load_weights_b")
+            self.load_opponent(opponent)
+
+    def load_weights(self, weights):
+        """(Re)load the network's weights -- player A's in an arena (kv_load_weights); empties its eval_cache."""
+        packed = packed_from(weights)
+        _lib.check(_lib.lib().kv_load_weights(self.h, packed.ctypes.data_as(C.POINTER(C.c_float)), packed.size),
+                   "kv_load_weights")
+
+    def load_opponent(self, weights):
+        """(Re)load player B's weights of an arena engine (kv_load_weights_b); empties B's eval_cache."""
+        packed = packed_from(weights)
+        _lib.check(_lib.lib().kv_load_weights_b(self.h, packed.ctypes.data_as(C.POINTER(C.c_float)), packed.size),
+                   "kv_load_weights_b")
 
     def run(self, max_steps: int = -1, stop_after_games: int = -1):
         _lib.check(_lib.lib().kv_run(self.h, int(max_steps), int(stop_after_games)), "kv_run")

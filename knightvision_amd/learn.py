@@ -73,7 +73,7 @@ def _dist():
 
 
 def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_moves=None, slots=256,
-                   precision="fp32", policy_targets=False, reuse_tree=False, leaves=0):
+                   precision="fp32", policy_targets=False, reuse_tree=False, leaves=0, eval_cache=0):
     """This rank's share of one iteration's games, played by the HIP engine with
     the model's current weights. Returns (records, games) numpy arrays; with
     policy_targets (MCTS runs) also the root visit counts and root move words of
@@ -81,7 +81,8 @@ def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_m
     [n, MAXM]) row for row, 0xffff past each position's move list. reuse_tree (sims > 0): the engine carries
     the subtree under each move played into the next ply (kv_config.reuse_tree); every root still holds sims
     visits, so the visit targets are built as without it. leaves > 1 (sims > 0): that many descents in flight
-    per game and sim-step (kv_config.leaves)."""
+    per game and sim-step (kv_config.leaves); eval_cache (leaves >= 2): entries of the engine's exact leaf-row cache
+    (kv_config.eval_cache; 0: off), which changes no record."""
     dist, rank, world = _dist()
     dev = torch.device(device)
     ids = list(range(rank, n_games, world))
@@ -95,7 +96,8 @@ def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_m
                         max_moves=max_moves, batch=SELFPLAY_BATCH, eps=EPSILON, alpha=ALPHA, sims=sims,
                         game_id_base=base, game_id_stride=world, device=dev.index or 0,
                         precision=precision, eval_mode=batched_eval_mode() if sims == 0 else 0,
-                        keep_root_moves=bool(policy_targets), reuse_tree=bool(reuse_tree), leaves=int(leaves)) as eng:
+                        keep_root_moves=bool(policy_targets), reuse_tree=bool(reuse_tree), leaves=int(leaves),
+                        eval_cache=int(eval_cache)) as eng:
         eng.run()
         selfplay_shard.last_calibration = eng.calibration()  # the conv paths these weights ran on
         selfplay_shard.last_stats = eng.stats()
@@ -105,7 +107,7 @@ def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_m
 
 
 def arena_shard(new_weights, old_weights, n_games: int, iteration: int, device, *, sims: int, max_moves=None,
-                slots=256, precision="fp32", leaves=0) -> dict:
+                slots=256, precision="fp32", leaves=0, eval_cache=0) -> dict:
     """A match of `n_games` games between the new weights (player A) and the old ones (player B), the games
     sharded over the ranks by global id as selfplay_shard shards them (game g of iteration i has the id
     i * n_games + g; A plays white in the even ids). Every rank returns the same arena.summarize of all the
@@ -119,7 +121,7 @@ def arena_shard(new_weights, old_weights, n_games: int, iteration: int, device, 
     if ids:
         r = arena.play_match(new_weights, old_weights, len(ids), sims=sims, slots=min(slots, len(ids)), seed=SEED,
                              max_moves=max_moves, device=dev.index or 0, game_id_base=iteration * n_games + rank,
-                             game_id_stride=world, precision=precision, leaves=leaves)
+                             game_id_stride=world, precision=precision, leaves=leaves, eval_cache=eval_cache)
         table, stats = r["game_table"], r["stats"]
     if dist is not None and world > 1:
         rows = torch.from_numpy(table.view(np.uint8).reshape(-1, GAME_DTYPE.itemsize).copy()).to(dev)
@@ -291,7 +293,8 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
                        accumulate_steps: int = T.ACCUM_STEPS, sims: int = 0, max_moves=None, slots: int = 256,
                        seed: int = 0, games_path: str | None = None, max_samples: int = 10000, log=print,
                        policy_target: str = "move", reuse_tree: bool = False, arena_games: int = 0,
-                       arena_sims: int | None = None, leaves: int = 0, arena_leaves: int | None = None):
+                       arena_sims: int | None = None, leaves: int = 0, arena_leaves: int | None = None,
+                       eval_cache: int = 0, arena_eval_cache: int | None = None):
     """Run the loop (learn.py reinforcement_loop :152-209); returns per-iteration statistics.
     `model` is a knightvision_amd.model.ChessNet (same parameters as ai/model.py) on `device`.
     `games_path`: the reference's JSONL dataset (ChessPGNDataset, :162) the self-play records extend --
@@ -309,7 +312,9 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
     arena.summarize of all ranks' games and "updated" (False: the iteration had nothing to train on, the match
     is the weights against themselves). Reporting only: no gating, no revert. 0: the loop as without it.
     `leaves` (sims > 0): descents in flight per game and sim-step in self-play (kv_config.leaves; 0 or 1: one);
-    `arena_leaves`: the same for the matches (None: `leaves`)."""
+    `arena_leaves`: the same for the matches (None: `leaves`).
+    `eval_cache` (leaves >= 2): entries of the self-play engine's exact leaf-row cache (kv_config.eval_cache; 0: off);
+    `arena_eval_cache`: the same per net for the matches (None: `eval_cache`). Neither changes a game."""
     if policy_target not in ("move", "visits"):
         raise ValueError(f"reinforcement_loop: policy_target {policy_target!r}: 'move' or 'visits'")
     if arena_games > 0 and (arena_sims if arena_sims is not None else sims) <= 0:
@@ -350,7 +355,8 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
             t0 = time.perf_counter()
             ar = arena_shard(packed_from(model), incumbent, arena_games, it, dev, max_moves=max_moves, slots=slots,
                              sims=arena_sims if arena_sims is not None else sims,
-                             leaves=arena_leaves if arena_leaves is not None else leaves)
+                             leaves=arena_leaves if arena_leaves is not None else leaves,
+                             eval_cache=arena_eval_cache if arena_eval_cache is not None else eval_cache)
             ar.pop("stats", None)
             ar["updated"] = n >= 2 * world
             st["arena"] = ar
@@ -360,11 +366,11 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
         if visits:
             recs, games, *pi = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves,
                                               slots=slots, policy_targets=True, reuse_tree=reuse_tree,
-                                              leaves=leaves)
+                                              leaves=leaves, eval_cache=eval_cache)
             pi = None if recs is None else tuple(pi)
         else:
             recs, games = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves, slots=slots,
-                                         reuse_tree=reuse_tree, leaves=leaves)
+                                         reuse_tree=reuse_tree, leaves=leaves, eval_cache=eval_cache)
         st["selfplay_s"] = time.perf_counter() - t0
         cal = getattr(selfplay_shard, "last_calibration", None)
         if cal is not None:  # fp32 AUTO: the self-play network's conv path for this iteration's weights

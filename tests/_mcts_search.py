@@ -163,6 +163,17 @@ CHECKMATED_ROOT = make_state({sq("g1"): 1, sq("a8"): 3, sq("g8"): 7, sq("f7"): 1
                              False)
 STALEMATE_ROOT = make_state({sq("f7"): 1, sq("g6"): 2, sq("h8"): 7}, False)
 KINGS_ONLY_ROOT = make_state({sq("e1"): 1, sq("e8"): 7}, True)
+# Roots wider than a wavefront, found by tools/find_wide_positions.py (seeded): queens on both sides, white to
+# move, black's king walled in on a1 so that no root move mates. 96, 137 and 206 root moves; WIDE_A and WIDE_B
+# have children of more than 64 moves (tests/test_mcts_wide_cpu.py asserts what the GPU tests rely on).
+WIDE_A = make_state({2: 2, 3: 2, 5: 2, 8: 1, 13: 2, 14: 8, 16: 2, 17: 2, 22: 2, 26: 8, 28: 8, 31: 8, 33: 8, 36: 2,
+                     40: 6, 41: 6, 42: 6, 45: 8, 48: 12, 49: 12, 50: 6, 51: 2, 56: 7, 57: 10, 58: 6}, True)
+WIDE_B = make_state({4: 2, 8: 8, 9: 2, 14: 2, 15: 1, 16: 2, 19: 2, 20: 2, 21: 2, 25: 8, 32: 8, 34: 2, 35: 8, 38: 8,
+                     40: 6, 41: 6, 42: 6, 44: 2, 46: 2, 48: 12, 49: 12, 50: 6, 52: 2, 53: 8, 56: 7, 57: 10, 58: 6,
+                     61: 2, 62: 2}, True)
+WIDE_C = make_state({0: 2, 1: 2, 2: 2, 3: 2, 4: 2, 5: 2, 6: 8, 7: 2, 8: 2, 14: 2, 16: 2, 20: 2, 23: 2, 26: 2, 31: 2,
+                     32: 1, 33: 2, 39: 2, 40: 6, 41: 6, 42: 6, 43: 2, 45: 2, 47: 2, 48: 12, 49: 12, 50: 6, 51: 2,
+                     55: 2, 56: 7, 57: 10, 58: 6, 60: 2, 62: 2, 63: 8}, True)
 
 
 class _Node:

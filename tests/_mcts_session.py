@@ -11,6 +11,8 @@ built from numpy float32 scalars in the kernel's operation order, so visits, q,
 priors and the principal variation must equal the device's bit for bit. Shared
 by the test_mcts_session_* modules and tests/test_mcts_search_net_gpu.py; not a
 test module itself."""
+import itertools
+
 import numpy as np
 
 from oracle import oracle as O
@@ -22,12 +24,16 @@ SEARCHED, CHECKMATED, STALEMATE, DRAW = S.SEARCHED, S.CHECKMATED, S.STALEMATE, S
 _SESSION = object()  # search / resume: the session's own evaluator
 
 
+_SERIAL = itertools.count()
+
+
 class _Node(S._Node):
-    __slots__ = ("value",)
+    __slots__ = ("value", "serial")
 
     def __init__(self, state, words, priors, value):
         super().__init__(state, words, priors)
         self.value = value  # the evaluator's value of the position, kept for a later re-root
+        self.serial = next(_SERIAL)  # creation order: a tree's later node has the larger device id
 
 
 class _Tree:

@@ -12,6 +12,9 @@ Fixtures written next to this script (data only; no reference source):
   movegen.npz   G1  ordered legal-move lists + inCheck for positions from seeded
                     random trajectories and hand-built quirk positions
                     (core/chessEngine.py:277-321, 388-394, makeMove :127-197)
+  movegen_wide.npz  the same for seeded hand-set boards of up to 229 moves (many queens, promotions in
+                    bulk, castling, en passant, pinned sliders, single and double checks), with the
+                    reference's own count of checkers and pins; `--wide-only` writes this file alone
   nn.npz        G3  ChessNet policy/value for fixed boards under the synthetic
                     weight variants (ai/model.py:51-77)
   games.npz     G4  full self-play games: move-index sequences, outcome/reward,
@@ -229,6 +232,282 @@ def gen_movegen(ce, n_traj=36, max_plies=260):
                 in_check=np.array(in_check, dtype=np.uint8), source=np.array(src, dtype=np.uint8))
 
 
+# ---------------------------------------------------------------- G1w wide movegen
+WIDE_RECORD = "R6R/3Q4/1Q4Q1/4Q3/2Q4Q/Q4Q2/pp1Q4/kBNN1KB1"  # white to move: 218 moves
+WIDE_MIN = dict(positions=400, over64=150, over128=40, atleast200=5, check_over30=30)
+WIDE_TAGS = ("record", "queens", "climb", "rooks_bishops", "promotions", "castling", "en_passant", "pinned",
+             "single_check", "double_check")
+
+
+def wide_stats(offsets, in_check, n_checks, source, states):
+    """The fixture's own quotas; asserted here and again by tests/test_oracle_golden.py."""
+    n = np.diff(offsets)
+    return dict(positions=len(n), over64=int((n > 64).sum()), over128=int((n > 128).sum()),
+                atleast200=int((n >= 200).sum()),
+                check_over30=int(((n_checks == 1) & (in_check == 1) & (n > 30)).sum()),
+                double_check=int((n_checks >= 2).sum()), white=int((states[:, 64] == 1).sum()),
+                black=int((states[:, 64] == 0).sum()), tags=sorted(set(int(t) for t in source)))
+
+
+def gen_movegen_wide(ce):
+    """Seeded hand-set boards far wider than any game position: the reference's ordered getValidMoves,
+    the state it leaves and inCheck, with its own count of checkers and pins (checkForPinsAndChecks)."""
+    tag_of = {t: i for i, t in enumerate(WIDE_TAGS)}
+    swap = {"w": "b", "b": "w"}
+    recs = []  # (tag, board, white, ep, castle)
+
+    def empty():
+        return [["--"] * 8 for _ in range(8)]
+
+    def flipped(board, ep):
+        # the same position with the colours swapped, seen from the other side
+        fb = [[("--" if p == "--" else swap[p[0]] + p[1]) for p in board[7 - r]] for r in range(8)]
+        return fb, (() if ep == () else (7 - ep[0], ep[1]))
+
+    def build(board, white, ep=(), castle=False):
+        gs = ce.GameState()
+        if not white:
+            board, ep = flipped(board, ep)
+        gs.board = [row[:] for row in board]
+        gs.whiteToMove = white
+        gs.enPassantPossible = ep
+        for r in range(8):
+            for c in range(8):
+                if gs.board[r][c] == "wK":
+                    gs.whiteKingLocation = (r, c)
+                if gs.board[r][c] == "bK":
+                    gs.blackKingLocation = (r, c)
+        for k in ("wKingMoved", "bKingMoved", "wRookKingsideMoved", "wRookQueensideMoved", "bRookKingsideMoved",
+                  "bRookQueensideMoved"):
+            setattr(gs, k, not castle)
+        return gs
+
+    def count(board, white=True, ep=(), castle=False):
+        return len(build(board, white, ep, castle).getValidMoves())
+
+    def scatter(rng, board, pieces, rows=range(8)):
+        free = [(r, c) for r in rows for c in range(8) if board[r][c] == "--"]
+        rng.shuffle(free)
+        for p, (r, c) in zip(pieces, free):
+            board[r][c] = p
+
+    def kings(rng, board, wk=None, bk=None):
+        # two kings that do not touch, on free squares
+        while True:
+            a = wk or (rng.randrange(8), rng.randrange(8))
+            b = bk or (rng.randrange(8), rng.randrange(8))
+            if max(abs(a[0] - b[0]), abs(a[1] - b[1])) > 1 and board[a[0]][a[1]] == "--" and board[b[0]][b[1]] == "--":
+                board[a[0]][a[1]], board[b[0]][b[1]] = "wK", "bK"
+                return a, b
+
+    def keep(tag, board, white, ep=(), castle=False):
+        recs.append((tag_of[tag], [row[:] for row in board], white, ep, castle))
+
+    # every board below is set up with white to move; odd ones are recorded colour-flipped with black to move
+    # the 218-move record, its file mirror, and both with the colours swapped
+    rec = empty()
+    for r, row in enumerate(WIDE_RECORD.split("/")):
+        c = 0
+        for ch in row:
+            if ch.isdigit():
+                c += int(ch)
+            else:
+                rec[r][c] = ("w" if ch.isupper() else "b") + (ch.upper() if ch.upper() != "P" else "p")
+                c += 1
+    for board in (rec, [row[::-1] for row in rec]):
+        for white in (True, False):
+            keep("record", board, white)
+    assert count(rec) == 218
+
+    # 14-25 queens of the mover, a few enemy pieces
+    rng = _pyrandom.Random(7001)
+    for t in range(150):
+        b = empty()
+        kings(rng, b)
+        scatter(rng, b, ["wQ"] * rng.randint(14, 25) + [rng.choice(["bQ", "bR", "bB", "bN", "bp"])
+                                                         for _ in range(rng.randint(0, 5))])
+        keep("queens", b, t % 2 == 0)
+
+    # hill climbs from such boards: move one queen wherever the list gets longer
+    rng = _pyrandom.Random(7002)
+    for t in range(6):
+        b = empty()
+        kings(rng, b)
+        scatter(rng, b, ["wQ"] * rng.randint(16, 20) + ["bp", "bp"])
+        white = t % 2 == 0
+        best = count(b, white)
+        for _ in range(260):
+            qs = [(r, c) for r in range(8) for c in range(8) if b[r][c] == "wQ"]
+            fr = [(r, c) for r in range(8) for c in range(8) if b[r][c] == "--"]
+            (r0, c0), (r1, c1) = rng.choice(qs), rng.choice(fr)
+            b[r0][c0], b[r1][c1] = "--", "wQ"
+            got = count(b, white)
+            if got >= best:
+                best = got
+            else:
+                b[r0][c0], b[r1][c1] = "wQ", "--"
+        keep("climb", b, white)
+
+    # rooks and bishops
+    rng = _pyrandom.Random(7003)
+    for t in range(50):
+        b = empty()
+        kings(rng, b)
+        scatter(rng, b, ["wR"] * rng.randint(4, 10) + ["wB"] * rng.randint(4, 10) + ["wN"] * rng.randint(0, 3) +
+                [rng.choice(["bR", "bB", "bN", "bp"]) for _ in range(rng.randint(2, 8))])
+        keep("rooks_bishops", b, t % 2 == 0)
+
+    # pawns on the seventh beside capturable pieces on the eighth
+    rng = _pyrandom.Random(7004)
+    for t in range(50):
+        b = empty()
+        kings(rng, b, wk=(rng.randint(5, 7), rng.randrange(8)), bk=(rng.randint(2, 3), rng.randrange(8)))
+        for c in range(8):
+            if rng.random() < 0.75:
+                b[1][c] = "wp"
+            if rng.random() < 0.6:
+                b[0][c] = rng.choice(["bQ", "bR", "bB", "bN"])
+        scatter(rng, b, ["wQ"] * rng.randint(0, 8) + ["wp"] * rng.randint(0, 3), rows=range(2, 7))
+        keep("promotions", b, t % 2 == 0)
+
+    # castling rights live, rooks at home
+    rng = _pyrandom.Random(7005)
+    for t in range(40):
+        b = empty()
+        b[7][4], b[0][4], b[7][0], b[7][7], b[0][0], b[0][7] = "wK", "bK", "wR", "wR", "bR", "bR"
+        scatter(rng, b, ["wQ"] * rng.randint(2, 12) + ["wB", "wN"] + [rng.choice(["bQ", "bB", "bN", "bp"])
+                                                                   for _ in range(rng.randint(0, 4))],
+                rows=range(1, 7))
+        if rng.random() < 0.3:
+            b[7][rng.choice([1, 2, 3, 5, 6])] = "wN"
+        keep("castling", b, t % 2 == 0, castle=True)
+
+    # an en-passant square: the enemy pawn has just gone two squares past the mover's
+    rng = _pyrandom.Random(7006)
+    for t in range(40):
+        b = empty()
+        c = rng.randrange(8)
+        b[3][c] = "bp"
+        for dc in (-1, 1):
+            if 0 <= c + dc < 8 and rng.random() < 0.8:
+                b[3][c + dc] = "wp"
+        kings(rng, b, wk=(rng.randint(5, 7), rng.randrange(8)), bk=(0, rng.randrange(8)))
+        scatter(rng, b, ["wQ"] * rng.randint(2, 12) + ["wR", "wp", "bp", "bN"], rows=range(3, 8))
+        keep("en_passant", b, t % 2 == 0, ep=(2, c))
+
+    # pinned sliders: king, own slider, enemy slider on one line
+    rng = _pyrandom.Random(7007)
+    dirs = [(-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (-1, 1), (1, -1), (1, 1)]
+    while sum(1 for r in recs if r[0] == tag_of["pinned"]) < 50:
+        b = empty()
+        kr, kc = rng.randrange(8), rng.randrange(8)
+        b[kr][kc] = "wK"
+        pins = 0
+        for dr, dc in rng.sample(dirs, rng.randint(1, 4)):
+            i, j = rng.randint(1, 3), rng.randint(1, 3)
+            r1, c1, r2, c2 = kr + dr * i, kc + dc * i, kr + dr * (i + j), kc + dc * (i + j)
+            if not (0 <= r2 < 8 and 0 <= c2 < 8):
+                continue
+            b[r1][c1] = rng.choice(["wQ", "wR", "wB"])
+            b[r2][c2] = rng.choice(["bQ", "bR"] if dr == 0 or dc == 0 else ["bQ", "bB"])
+            pins += 1
+        free = [(r, c) for r in range(8) for c in range(8) if b[r][c] == "--" and max(abs(r - kr), abs(c - kc)) > 1]
+        r, c = rng.choice(free)
+        b[r][c] = "bK"
+        scatter(rng, b, ["wQ"] * rng.randint(3, 12))
+        white = len(recs) % 2 == 0
+        _, got, _ = build(b, white).checkForPinsAndChecks()
+        if pins and len(got) >= 1:
+            keep("pinned", b, white)
+
+    # the mover in single check from a slider, with many pieces that could block or capture
+    rng = _pyrandom.Random(7008)
+    wide_checks = 0
+    while sum(1 for r in recs if r[0] == tag_of["single_check"]) < 70:
+        b = empty()
+        kr, kc = rng.randrange(8), rng.randrange(8)
+        dr, dc = rng.choice(dirs)
+        i = rng.randint(5 if wide_checks < 40 else 3, 7)
+        r1, c1 = kr + dr * i, kc + dc * i
+        if not (0 <= r1 < 8 and 0 <= c1 < 8):
+            continue
+        b[kr][kc] = "wK"
+        b[r1][c1] = rng.choice(["bQ", "bR"] if dr == 0 or dc == 0 else ["bQ", "bB"])
+        line = {(kr + dr * k, kc + dc * k) for k in range(1, i)}
+        free = [(r, c) for r in range(8) for c in range(8) if b[r][c] == "--" and (r, c) not in line]
+        far = [s for s in free if max(abs(s[0] - kr), abs(s[1] - kc)) > 1]
+        r, c = rng.choice(far)
+        b[r][c] = "bK"
+        free.remove((r, c))
+        rng.shuffle(free)
+        for p, (r, c) in zip(["wQ"] * rng.randint(6, 24) + ["wR", "wB", "wN", "wp"], free):
+            b[r][c] = p
+        white = len(recs) % 2 == 0
+        gs = build(b, white)
+        chk, _, checks = gs.checkForPinsAndChecks()
+        if chk and len(checks) == 1:
+            got = len(gs.getValidMoves())
+            if wide_checks < 40 and got <= 30:
+                continue  # the first 40 kept have more than 30 answers to the check
+            wide_checks += got > 30
+            keep("single_check", b, white)
+
+    # the mover in double check
+    rng = _pyrandom.Random(7009)
+    while sum(1 for r in recs if r[0] == tag_of["double_check"]) < 30:
+        b = empty()
+        kr, kc = rng.randrange(8), rng.randrange(8)
+        b[kr][kc] = "wK"
+        ok = 0
+        for dr, dc in rng.sample(dirs, 2):
+            i = rng.randint(2, 6)
+            r1, c1 = kr + dr * i, kc + dc * i
+            if 0 <= r1 < 8 and 0 <= c1 < 8 and b[r1][c1] == "--":
+                b[r1][c1] = rng.choice(["bQ", "bR"] if dr == 0 or dc == 0 else ["bQ", "bB"])
+                ok += 1
+        if ok < 2:
+            continue
+        free = [(r, c) for r in range(8) for c in range(8) if b[r][c] == "--" and max(abs(r - kr), abs(c - kc)) > 1]
+        r, c = rng.choice(free)
+        b[r][c] = "bK"
+        scatter(rng, b, ["wQ"] * rng.randint(2, 8))
+        white = len(recs) % 2 == 0
+        _, _, checks = build(b, white).checkForPinsAndChecks()
+        if len(checks) >= 2:
+            keep("double_check", b, white)
+
+    states, post, offsets, moves, in_check, src, n_checks, n_pins = [], [], [0], [], [], [], [], []
+    for tag, board, white, ep, castle in recs:
+        gs = build(board, white, ep, castle)
+        _, pins, checks = gs.checkForPinsAndChecks()
+        states.append(state_vec(gs))
+        ml = gs.getValidMoves()
+        post.append(state_vec(gs))
+        moves.extend(move_triplet(m) for m in ml)
+        offsets.append(len(moves))
+        in_check.append(1 if gs.inCheck() else 0)
+        src.append(tag)
+        n_checks.append(len(checks))
+        n_pins.append(len(pins))
+    out = dict(states=np.stack(states), post_states=np.stack(post), offsets=np.array(offsets, dtype=np.int32),
+               moves=np.array(moves, dtype=np.uint8).reshape(-1, 3), in_check=np.array(in_check, dtype=np.uint8),
+               source=np.array(src, dtype=np.uint8), n_checks=np.array(n_checks, dtype=np.uint8),
+               n_pins=np.array(n_pins, dtype=np.uint8))
+    st = wide_stats(out["offsets"], out["in_check"], out["n_checks"], out["source"], out["states"])
+    print("movegen_wide", st, "widest", int(np.diff(out["offsets"]).max()))
+    for k, v in WIDE_MIN.items():
+        assert st[k] >= v, (k, st[k], v)
+    assert st["tags"] == list(range(len(WIDE_TAGS))) and st["double_check"] >= 20
+    assert min(st["white"], st["black"]) >= 150
+    assert int((out["n_pins"] > 0).sum()) >= 40
+    mv, off = out["moves"], out["offsets"]
+    assert int((mv[:, 2] & 4 != 0).sum()) >= 100, "promotions"
+    assert int((mv[:, 2] & 2 != 0).sum()) >= 20, "castling moves"
+    assert int((mv[:, 2] & 1 != 0).sum()) >= 20, "en-passant captures"
+    assert int(np.diff(off).max()) <= 255
+    return out
+
+
 # ---------------------------------------------------------------- G3 NN
 def planes_from_state(ref_ai, v):
     board = [[PIECES[int(v[r * 8 + c])] for c in range(8)] for r in range(8)]
@@ -369,8 +648,12 @@ def gen_unittests(ce):
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     nn_only = "--nn-only" in sys.argv  # regenerate nn.npz from the committed movegen.npz positions
+    wide_only = "--wide-only" in sys.argv  # write movegen_wide.npz alone; every other fixture stays as it is
     ref = args[0] if args else "/root/reference"
     sp, ce, ref_model, ref_ai = import_reference(ref)
+    if wide_only:
+        np.savez_compressed(os.path.join(HERE, "movegen_wide.npz"), **gen_movegen_wide(ce))
+        return
     import torch
     torch.set_num_threads(8)
 
@@ -400,6 +683,7 @@ def main():
 
     with open(os.path.join(HERE, "unittests.json"), "w") as f:
         json.dump(gen_unittests(ce), f)
+    np.savez_compressed(os.path.join(HERE, "movegen_wide.npz"), **gen_movegen_wide(ce))
     print("done")
 
 

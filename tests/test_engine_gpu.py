@@ -73,6 +73,85 @@ def test_device_make_move_matches_oracle(golden_dir):
         assert np.array_equal(dev[k], O.make_valid_move(states[i], int(choice[k]))), i
 
 
+@pytest.fixture(scope="module")
+def wide(golden_dir):
+    """tests/golden/movegen_wide.npz: hand-set boards of up to 229 moves from the reference."""
+    g = np.load(os.path.join(golden_dir, "movegen_wide.npz"))
+    return {k: g[k] for k in ("states", "post_states", "offsets", "moves", "in_check")}
+
+
+def test_device_movegen_matches_reference_wide(wide):
+    """wave_valid_moves where its 64-strided loops run two to four times: every position in one call."""
+    states, post, offs, moves, chk = (wide[k] for k in ("states", "post_states", "offsets", "moves", "in_check"))
+    dm, nm, after, dchk = dev_valid_moves(states)
+    assert nm.tolist() == np.diff(offs).tolist()
+    bad = []
+    for i in range(len(states)):
+        want = moves[offs[i]:offs[i + 1]]
+        got = to_triplets(dm[i, :nm[i]])
+        if not (np.array_equal(got, want) and np.array_equal(after[i], post[i]) and dchk[i] == chk[i]):
+            bad.append(i)
+    assert not bad, f"{len(bad)}/{len(states)} positions differ; first {bad[:5]}"
+
+
+def test_device_make_move_matches_oracle_wide(wide):
+    """Three move indices per position: the last, a seeded one at 64 or above wherever the list is that long
+    (below it otherwise), and a seeded one anywhere."""
+    from oracle import oracle as O
+    states, n_moves = wide["states"], np.diff(wide["offsets"])
+    rng = np.random.default_rng(1)
+    idx = np.flatnonzero(n_moves > 0)
+    n = n_moves[idx]
+    high = np.where(n > 64, 64 + (rng.random(len(idx)) * (n - 64)).astype(np.int64),
+                    (rng.random(len(idx)) * n).astype(np.int64))
+    picks = [n - 1, high, (rng.random(len(idx)) * n).astype(np.int64)]
+    assert ((picks[1] >= 64) == (n > 64)).all() and (n > 64).sum() >= 150
+    for choice in picks:
+        choice = np.ascontiguousarray(choice, dtype=np.int32)
+        assert ((choice >= 0) & (choice < n)).all()
+        dev = states[idx].copy()
+        _lib.check(_lib.lib().kv_dev_make_move(0, _p(dev, C.c_int8), _p(choice, C.c_int), len(idx)),
+                   "kv_dev_make_move")
+        for k, i in enumerate(idx):
+            assert np.array_equal(dev[k], O.make_valid_move(states[i], int(choice[k]))), (i, int(choice[k]))
+
+
+def test_device_attacks_match_reference_in_check_wide(wide):
+    """kv_dev_attacks on the states getValidMoves leaves: the bit of the mover's stored king square is the
+    reference's inCheck (the oracle exposes no attack set to compare the other 63 bits with)."""
+    post, chk = np.ascontiguousarray(wide["post_states"]), wide["in_check"]
+    att = np.zeros(len(post), dtype=np.uint64)
+    _lib.check(_lib.lib().kv_dev_attacks(0, _p(post, C.c_int8), len(post), _p(att, C.c_uint64)), "kv_dev_attacks")
+    wtm = post[:, 64] == 1
+    ksq = np.where(wtm, post[:, 65] * 8 + post[:, 66], post[:, 67] * 8 + post[:, 68]).astype(np.uint64)
+    got = ((att >> ksq) & np.uint64(1)).astype(np.uint8)
+    assert chk.sum() >= 90 and (chk == 0).sum() >= 90
+    assert got.tolist() == chk.tolist()
+
+
+def test_device_valid_moves_cap_contract(wide):
+    """A list longer than `cap`: n_moves is -n, the first cap words are the uncapped list's, and the state after
+    and inCheck do not depend on cap. Ten wide positions and the initial one, cap below, at and above 64."""
+    from oracle import oracle as O
+    n_all = np.diff(wide["offsets"])
+    order = np.argsort(-n_all[1:], kind="stable") + 1  # widest first; position 0 (the 218-move record) apart
+    pick = [0] + order[[0, 5, 12, 30, 60]].tolist() + np.flatnonzero((n_all > 64) & (n_all < 80))[:2].tolist() + \
+        np.flatnonzero((n_all > 128) & (n_all < 140))[:2].tolist()
+    assert len(set(pick)) == 10 and (n_all[pick] > 64).all()
+    states = np.concatenate([wide["states"][pick], O.initial_state()[None]])
+    full, n_full, after_full, chk_full = dev_valid_moves(states)
+    assert n_full[:10].tolist() == n_all[pick].tolist() and n_full[10] == 20
+    for k, st in enumerate(states):
+        n = int(n_full[k])
+        for cap in sorted({1, 16, 63, 64, 65, n - 1, n}):
+            dm, nm, after, chk = dev_valid_moves(st[None], cap=cap)
+            tag = (k, n, cap)
+            assert nm[0] == (-n if cap < n else n), tag
+            m = min(cap, n)
+            assert dm[0, :m].tolist() == full[k, :m].tolist(), tag
+            assert np.array_equal(after[0], after_full[k]) and chk[0] == chk_full[k], tag
+
+
 @pytest.mark.parametrize("alpha", [0.3, 0.03, 0.01])
 def test_device_dirichlet_stream_matches_numpy(alpha):
     """DIR_NOISE_ALPHA (scripts/self_play.py:13) is configurable; below 53/1022

@@ -33,6 +33,40 @@ def test_movegen_matches_reference(movegen):
     assert not bad, f"{len(bad)} positions differ, first {bad[:5]}"
 
 
+def test_wide_fixture_holds_what_it_was_made_for(golden_dir):
+    """tests/golden/movegen_wide.npz (make_golden.py --wide-only): the quotas its generator asserts, again, so
+    a regenerated fixture cannot quietly lose the wide, checked or special-move positions."""
+    g = np.load(os.path.join(golden_dir, "movegen_wide.npz"))
+    st, offs, mv = g["states"], g["offsets"], g["moves"]
+    n = np.diff(offs)
+    assert len(st) >= 400 and len(st) == len(g["post_states"]) == len(g["in_check"]) == len(n)
+    assert (n > 64).sum() >= 150 and (n > 128).sum() >= 40 and (n >= 200).sum() >= 5 and n.max() <= 255
+    assert min((st[:, 64] == 1).sum(), (st[:, 64] == 0).sum()) >= 150  # both colours to move
+    single = (g["n_checks"] == 1) & (g["in_check"] == 1)
+    assert (single & (n > 30)).sum() >= 30
+    assert (g["n_checks"] >= 2).sum() >= 20 and (g["n_pins"] > 0).sum() >= 40
+    assert set(g["source"].tolist()) == set(range(10))  # every kind of board the generator builds
+    assert (mv[:, 2] & 4 != 0).sum() >= 100 and (mv[:, 2] & 2 != 0).sum() >= 20 and (mv[:, 2] & 1 != 0).sum() >= 20
+    assert (st[:, 75] >= 0).sum() >= 30 and (st[:, 69:75] == 0).all(axis=1).sum() >= 30  # ep squares, castling rights
+    # R6R/3Q4/1Q4Q1/4Q3/2Q4Q/Q4Q2/pp1Q4/kBNN1KB1 w, the 218-move record, is the first position
+    assert n[0] == 218 and st[0, 64] == 1 and st[0, :8].tolist() == [3, 0, 0, 0, 0, 0, 0, 3]
+    assert os.path.getsize(os.path.join(golden_dir, "movegen_wide.npz")) < 256 * 1024
+
+
+def test_wide_movegen_matches_reference(golden_dir):
+    """The C oracle at move lists of up to 229 moves: ordered moves, the state getValidMoves leaves, inCheck."""
+    g = np.load(os.path.join(golden_dir, "movegen_wide.npz"))
+    states, post, offs, moves, chk = (g[k] for k in ("states", "post_states", "offsets", "moves", "in_check"))
+    bad = []
+    for i in range(len(states)):
+        got, st_after = O.valid_moves(states[i])
+        want = moves[offs[i]:offs[i + 1]]
+        if got.shape != want.shape or not np.array_equal(got, want) or not np.array_equal(st_after, post[i]) \
+                or O.in_check(st_after) != bool(chk[i]):
+            bad.append(i)
+    assert not bad, f"{len(bad)} positions differ, first {bad[:5]}"
+
+
 def test_unittest_scenarios(golden_dir):
     cases = json.load(open(os.path.join(golden_dir, "unittests.json")))
     for c in cases:

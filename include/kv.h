@@ -554,8 +554,21 @@ int kv_dev_i8gemm_bench(int device, int rows, int K, int variant, int iters, flo
  * digits) back to back for `seconds`, then
  * one launch of its stamped build: out[0] = median over workgroups of (s_memtime delta / s_memrealtime delta)
  * x 100 MHz, out[1] = the back-to-back launches' mean time (us), out[2] = their count, out[3] = tiles per
- * workgroup of the stamped kernel. */
+ * workgroup of the stamped kernel, which runs on the product launch's grid. */
 int kv_dev_gemm_clock(int device, int rows, int digits, double seconds, double* out);
+/* kv_dev_gemm_clock for KV_ALGO_WINOGRAD88_I8R3's GEMM with the tower's CU share (`share` 2: the grid sized for
+ * half the CUs, as with two slot groups side by side; 1: the whole chip) and, abl 16, the timing ablation that
+ * compiles the tile epilogue out (no conversion, no M stores; M is not written), which only this entry reaches.
+ * out[0..3] as kv_dev_gemm_clock, out[4] = workgroups of the launch (the product's one-round grid). */
+int kv_dev_r3gemm_clock(int device, int rows, int abl, int share, double seconds, double* out);
+/* KV_ALGO_WINOGRAD88_I8R3's slice kernel and GEMM on a slice of a longer buffer: V [100][rows][K] and U
+ * [100][512][K] fp64 (K 256 or 512); the digits, exponents and M occupy rows [row0, row0 + rows) of buffers
+ * `stride` rows long (all multiples of 128, stride at most 16,384), as a forward's slices do. tpw 0: the
+ * product's kernel and grid for `rows`; 1, 4 or 5: that many tiles per workgroup in nwg workgroups (0: the
+ * launcher's grid; else a multiple of 8 with 400 rows / 128 = tpw x nwg x groups). M [100][rows][512] returns
+ * those rows (fp32, widened); *outside = how many elements of M's other rows the launch changed. */
+int kv_dev_wino88i_r3(int device, const double* V, int rows, const double* U, int K, int tpw, int nwg, int stride,
+                      int row0, double* M, long long* outside);
 /* Phase timing of the fp32 tower's output kernel (a diagnostic build of wino88i32_out_kernel with shader-clock
  * stamps) at `rows` boards on seeded M (resid: the residual + Y variant; r3: 3 radix-256 digits): stamps
  * [min(rows, 4096)][2][6] = s_memtime of waves 0 and 15 of each board's workgroup at start, V ready, after the

@@ -153,6 +153,8 @@ def _declare(L):
         "kv_dev_wino88i": ([i, P(C.c_double), i, P(C.c_double), i, i, i, P(C.c_double), P(C.c_int8), P(i)], i),
         "kv_dev_i8gemm_bench": ([i, i, i, i, i, P(C.c_float), P(C.c_float)], i),
         "kv_dev_gemm_clock": ([i, i, i, C.c_double, P(C.c_double)], i),
+        "kv_dev_r3gemm_clock": ([i, i, i, i, C.c_double, P(C.c_double)], i),
+        "kv_dev_wino88i_r3": ([i, P(C.c_double), i, P(C.c_double), i, i, i, i, i, P(C.c_double), P(i64)], i),
         "kv_dev_net_pair": ([vp, vp, i, i], i),
         "kv_dev_out_phases": ([i, i, i, i, P(C.c_uint64), P(C.c_float)], i),
         "kv_dev_wino88i32_out": ([i, P(C.c_float), i, P(C.c_float), P(C.c_float), P(C.c_float), i, P(C.c_float),
@@ -203,7 +205,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_search", "kv_sizeof_search_result", "kv_search_advance", "kv_search_continue", "kv_search_tree_size",
             "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm", "kv_dev_eval_cache",
             "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_tower_front", "kv_dev_tower_back", "kv_dev_i8gemm_bench",
-            "kv_dev_gemm_clock", "kv_dev_out_phases", "kv_dev_net_pair",
+            "kv_dev_gemm_clock", "kv_dev_r3gemm_clock", "kv_dev_wino88i_r3", "kv_dev_out_phases", "kv_dev_net_pair",
             "kv_pgn_extract", "kv_fen_codes", "kv_san_move_index", "kv_chess_perft", "kv_chess_san", "kv_chess_fen",
             "kv_tr_conv3x3_f16", "kv_tr_conv3x3_add_f16", "kv_tr_conv_weights_f16", "kv_tr_wgrad_workspace", "kv_tr_conv3x3_wgrad_f16",
             "kv_tr_bn_workspace", "kv_tr_bn_stats_f16", "kv_tr_bn_apply_f16", "kv_tr_bn_backward_f16",

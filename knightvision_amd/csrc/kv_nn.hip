@@ -1178,10 +1178,19 @@ static int launch_wino88i32_gemm_lagt(const int8_t* V8, const int* ev, const int
     return KV_OK;
 }
 
-// R3's GEMM with 64-k stages (kv_wino88i.h wino88i32_gemm_r3k64_kernel): 3 x 48 KiB of LDS
+// the R3 GEMM's grid for `tiles` tiles in groups of tpw. One round: when the groups fill whole rounds of the CUs
+// (this launch's share of them), one workgroup per CU runs all its rounds' groups back to back, the copy ring
+// running across them (no prologue between them)
+static int r3k64_grid(int tiles, int tpw, int share) {
+    const int nwg = tiles / tpw, cus = gemm_cus(share);
+    return r3_one_round() && cus > 0 && cus % 8 == 0 && nwg > cus && nwg % cus == 0 ? cus : nwg;
+}
+
+// R3's GEMM with 64-k stages (kv_wino88i.h wino88i32_gemm_r3k64_kernel): 3 x 48 KiB of LDS. force_nwg (the dev
+// entries only): that many workgroups instead of r3k64_grid's
 template <int K, int TPW>
 static int launch_wino88i32_gemm_r3k64(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, float* M,
-                                       int rows, int stride, hipStream_t st, int share = 1) {
+                                       int rows, int stride, hipStream_t st, int share = 1, int force_nwg = 0) {
     constexpr int bytes = 3 * 4 * 128 * 96 + 2 * TPW * 1024;  // the ring + two groups' tile exponents
     auto kern = kv::wino88i32_gemm_r3k64_kernel<K, TPW>;
     if constexpr (K == 512 && TPW == 5) {  // KV_R3K64_ABL: timing ablations (outputs invalid; A/B tooling only)
@@ -1200,11 +1209,7 @@ static int launch_wino88i32_gemm_r3k64(const int8_t* V8, const int* ev, const in
     const int tiles = kv::W88_XI * (rows / 128) * (512 / 128);
     KV_REQUIRE(rows % 128 == 0 && stride % 128 == 0 && tiles % (8 * TPW) == 0, KV_EINVAL,
                "wino gemm i8 (r3k64): rows %d / stride %d vs tile 128", rows, stride);
-    // one round: when the TPW-tile groups fill whole rounds of the CUs, one workgroup per CU runs all its rounds'
-    // groups back to back, the copy ring running across them (no prologue between them)
-    int nwg = tiles / TPW;
-    const int cus = gemm_cus(share);
-    if (r3_one_round() && cus > 0 && cus % 8 == 0 && nwg > cus && nwg % cus == 0) nwg = cus;
+    const int nwg = force_nwg > 0 ? force_nwg : r3k64_grid(tiles, TPW, share);
     KV_REQUIRE(nwg % 8 == 0 && tiles % (nwg * TPW) == 0, KV_EINVAL, "wino gemm i8 (r3k64): %d tiles, %d workgroups",
                tiles, nwg);
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(512), bytes, st, V8, ev, U8, eu, M, rows, 512, stride, nullptr);
@@ -2387,6 +2392,98 @@ int kv_dev_wino88i(int device, const double* V, int rows, const double* U, int K
     return KV_OK;
 }
 
+constexpr unsigned kDevMFill = 0x7fc0de01u;  // kv_dev_wino88i_r3's M before the GEMM: a NaN no product gives
+
+// elements of M [xi][stride][512] in rows outside [row0, row0 + rows) of their xi that no longer hold kDevMFill
+__global__ void dev_m_outside_kernel(const unsigned* __restrict__ M, size_t n, int stride, int row0, int rows,
+                                     unsigned long long* __restrict__ count) {
+    unsigned long long c = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int row = (int)((i >> 9) % (size_t)stride);
+        if ((row < row0 || row >= row0 + rows) && M[i] != kDevMFill) ++c;
+    }
+    if (c) atomicAdd(count, c);
+}
+
+// R3's slice kernel and 64-k-stage GEMM as the tower runs them on a slice of a larger buffer: `rows` rows of V
+// at rows [row0, row0 + rows) of buffers `stride` rows long (digits [100][K/32][stride][96], exponents
+// [100][stride], M [100][stride][512]). tpw 0: the product's kernel and grid for `rows` (i8f32_gemm); 1, 4 or 5:
+// that many tiles per workgroup in nwg workgroups (0: the launcher's grid), so one launch at 128 rows reaches the
+// group loop and the ring across groups. M returns those rows [100][rows][512] widened; *outside the number of
+// M's other elements the launch changed (0 unless the kernel wrote out of its tiles).
+int kv_dev_wino88i_r3(int device, const double* V, int rows, const double* U, int K, int tpw, int nwg, int stride,
+                      int row0, double* M, long long* outside) {
+    KV_REQUIRE(V && U && M && outside && rows > 0 && rows % 128 == 0 && (K == 256 || K == 512) && stride % 128 == 0 &&
+                   stride <= kMaxBoards && row0 >= 0 && row0 % 128 == 0 && row0 + rows <= stride &&
+                   (tpw == 0 || tpw == 1 || tpw == 4 || tpw == 5) && nwg >= 0 && (tpw || !nwg),
+               KV_EINVAL, "kv_dev_wino88i_r3: bad arguments (rows %d at row %d of %d: multiples of 128, at most %d; "
+               "K %d 256 or 512; tpw %d 0, 1, 4 or 5; %d workgroups only with a tpw)",
+               rows, row0, stride, kMaxBoards, K, tpw, nwg);
+    KV_HIP(hipSetDevice(device));
+    constexpr int X = kv::W88_XI, D = kv::kI8DigitsF32;
+    const size_t nv = (size_t)X * rows * K, nu = (size_t)X * 512 * K;
+    const size_t nms = (size_t)X * stride * 512, line = 96;
+    kv::DevBuf<double> dv, du;
+    kv::DevBuf<float> dm;
+    kv::DevBuf<int8_t> v8c, v8s, u8;
+    kv::DevBuf<int> evc, evs, eu;
+    kv::DevBuf<unsigned long long> cnt;
+    KV_HIP(dv.alloc(nv));
+    KV_HIP(du.alloc(nu));
+    KV_HIP(v8c.alloc(nv * D));
+    KV_HIP(u8.alloc(nu * D));
+    KV_HIP(evc.alloc((size_t)X * rows));
+    KV_HIP(eu.alloc((size_t)X * 512));
+    KV_HIP(v8s.alloc((size_t)X * (K / 32) * stride * line));
+    KV_HIP(evs.alloc((size_t)X * stride));
+    KV_HIP(dm.alloc(nms));
+    KV_HIP(cnt.alloc(1));
+    KV_HIP(hipMemset(v8s.p, 0, (size_t)X * (K / 32) * stride * line));
+    KV_HIP(hipMemset(evs.p, 0, (size_t)X * stride * sizeof(int)));
+    KV_HIP(hipMemset(cnt.p, 0, sizeof(unsigned long long)));
+    KV_HIP(hipMemsetD32((hipDeviceptr_t)dm.p, (int)kDevMFill, nms));
+    KV_HIP(hipMemcpy(dv.p, V, nv * sizeof(double), hipMemcpyHostToDevice));
+    KV_HIP(hipMemcpy(du.p, U, nu * sizeof(double), hipMemcpyHostToDevice));
+    int rc = K == 256 ? launch_wino88i_slice<256, D, double, 1, false, true>(du.p, 512, 512, X, u8.p, eu.p, 0)
+                      : launch_wino88i_slice<512, D, double, 1, false, true>(du.p, 512, 512, X, u8.p, eu.p, 0);
+    if (!rc)
+        rc = K == 256 ? launch_wino88i_slice<256, D, double, 1, false, true>(dv.p, rows, rows, X, v8c.p, evc.p, 0)
+                      : launch_wino88i_slice<512, D, double, 1, false, true>(dv.p, rows, rows, X, v8c.p, evc.p, 0);
+    if (rc) return rc;
+    // the compact lines and exponents into rows [row0, row0 + rows) of the strided buffers
+    KV_HIP(hipMemcpy2D(v8s.p + (size_t)row0 * line, (size_t)stride * line, v8c.p, (size_t)rows * line,
+                       (size_t)rows * line, (size_t)X * (K / 32), hipMemcpyDeviceToDevice));
+    KV_HIP(hipMemcpy2D(evs.p + row0, (size_t)stride * sizeof(int), evc.p, (size_t)rows * sizeof(int),
+                       (size_t)rows * sizeof(int), X, hipMemcpyDeviceToDevice));
+    const int8_t* v8 = v8s.p + (size_t)row0 * line;
+    const int* ev = evs.p + row0;
+    float* m = dm.p + (size_t)row0 * 512;
+    auto gemm = [&](auto kc) -> int {
+        constexpr int KK = decltype(kc)::value;
+        switch (tpw) {
+            case 0: return i8f32_gemm<KK>(v8, ev, u8.p, eu.p, m, rows, stride, false, 0, true);
+            case 1: return launch_wino88i32_gemm_r3k64<KK, 1>(v8, ev, u8.p, eu.p, m, rows, stride, 0, 1, nwg);
+            case 4: return launch_wino88i32_gemm_r3k64<KK, 4>(v8, ev, u8.p, eu.p, m, rows, stride, 0, 1, nwg);
+            default: return launch_wino88i32_gemm_r3k64<KK, 5>(v8, ev, u8.p, eu.p, m, rows, stride, 0, 1, nwg);
+        }
+    };
+    rc = K == 256 ? gemm(std::integral_constant<int, 256>{}) : gemm(std::integral_constant<int, 512>{});
+    if (rc) return rc;
+    hipLaunchKernelGGL(dev_m_outside_kernel, dim3(2048), dim3(256), 0, 0, (const unsigned*)dm.p, nms, stride, row0,
+                       rows, cnt.p);
+    KV_HIP(hipGetLastError());
+    KV_HIP(hipDeviceSynchronize());
+    unsigned long long c = 0;
+    KV_HIP(hipMemcpy(&c, cnt.p, sizeof(c), hipMemcpyDeviceToHost));
+    *outside = (long long)c;
+    std::vector<float> mf((size_t)X * rows * 512);
+    for (int x = 0; x < X; ++x)
+        KV_HIP(hipMemcpy(mf.data() + (size_t)x * rows * 512, m + (size_t)x * stride * 512,
+                         (size_t)rows * 512 * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < mf.size(); ++i) M[i] = mf[i];
+    return KV_OK;
+}
+
 }  // extern "C"
 
 // the per-row fused output kernel of kv_dev_wino88i32_out: the held-V form (hold) or the product's default
@@ -2757,11 +2854,26 @@ int kv_dev_i8gemm_bench(int device, int rows, int K, int variant, int iters, flo
 // for `seconds`, then ONE launch of the stamped build of the same kernel (wino88i32_gemm_lagt_kernel<., TPW, .,
 // true>; TPW 1 where the product runs single tiles): per workgroup (s_memtime delta) / (s_memrealtime delta)
 // x 100 MHz, the median over workgroups. out[0] = that clock in MHz, out[1] = the back-to-back launches'
-// mean time in us (HIP events), out[2] = launches timed, out[3] = tiles per workgroup of the stamped build.
-int kv_dev_gemm_clock(int device, int rows, int digits, double seconds, double* out) {
-    KV_REQUIRE(rows > 0 && rows % 128 == 0 && rows <= kMaxBoards && (digits == 3 || digits == 4) && seconds > 0 && out,
-               KV_EINVAL, "kv_dev_gemm_clock: bad arguments (rows %d: a multiple of 128, at most %d; digits %d: 3 or 4)",
-               rows, kMaxBoards, digits);
+// mean time in us (HIP events), out[2] = launches timed, out[3] = tiles per workgroup of the stamped build,
+// out[4] = its workgroups. The stamped launch has the product launch's grid (R3: the one-round grid of
+// r3k64_grid on this launch's share of the CUs, as launch_wino88i32_gemm_r3k64).
+// kv_dev_r3gemm_clock (digits 3 only): `share` as the tower passes it when two slot groups run side by side (2:
+// half the CUs), and abl 16: the timing ablation without the tile epilogue (wino88i32_gemm_r3k64_kernel's ABL;
+// M is not written) in the loop and in the stamped launch -- reachable through this entry alone.
+}  // extern "C"
+
+template <int TPW>
+static auto r3k64_dev_kernel(bool stamp, bool abl) {
+    return stamp ? (abl ? kv::wino88i32_gemm_r3k64_kernel<512, TPW, true, 16> : kv::wino88i32_gemm_r3k64_kernel<512, TPW, true>)
+                 : (abl ? kv::wino88i32_gemm_r3k64_kernel<512, TPW, false, 16> : kv::wino88i32_gemm_r3k64_kernel<512, TPW>);
+}
+
+static int gemm_clock(int device, int rows, int digits, int abl, int share, double seconds, double* out) {
+    KV_REQUIRE(rows > 0 && rows % 128 == 0 && rows <= kMaxBoards && (digits == 3 || digits == 4) && seconds > 0 && out &&
+                   (abl == 0 || (abl == 16 && digits == 3)) && (share == 1 || (share == 2 && digits == 3)),
+               KV_EINVAL, "kv_dev_gemm_clock: bad arguments (rows %d: a multiple of 128, at most %d; digits %d: 3 or 4; "
+               "abl %d: 0, or 16 with 3 digits; share %d: 1, or 2 with 3 digits)",
+               rows, kMaxBoards, digits, abl, share);
     const bool r3 = digits == 3;
     KV_HIP(hipSetDevice(device));
     constexpr int K = 512;
@@ -2781,9 +2893,29 @@ int kv_dev_gemm_clock(int device, int rows, int digits, double seconds, double* 
     hipLaunchKernelGGL(i8_fill_kernel, dim3((unsigned)((lu * 128 + 255) / 256)), dim3(256), 0, 0, u8.p, lu, eu.p,
                        (size_t)kv::W88_XI * 512, 99u);
     KV_HIP(hipGetLastError());
+    // the form the product launches for `rows` (R3: the 64-k-stage kernel on its one-round grid)
+    using T = kv::Wino88iTile<kv::kI8DigitsF32>;
+    const int tpw = i8f32_tiles_per_wg(rows, share) >= 4 ? i8f32_tiles_per_wg(rows, share) : 1;
+    const int tiles = kv::W88_XI * (rows / T::WM) * (512 / T::WN);
+    KV_REQUIRE(tiles % (8 * tpw) == 0, KV_EINVAL, "kv_dev_gemm_clock: %d tiles, %d per workgroup", tiles, tpw);
+    const int nwg = r3 ? r3k64_grid(tiles, tpw, tpw >= 4 ? share : 1) : tiles / tpw;
+    const int bytes = r3 ? 3 * 4 * 128 * 96 + 2 * tpw * 1024 : KV_I8F32_NB * T::STAGE;
+    auto r3kern = [&](bool stamp) {
+        return tpw == 5 ? r3k64_dev_kernel<5>(stamp, abl != 0)
+               : tpw == 4 ? r3k64_dev_kernel<4>(stamp, abl != 0)
+                          : r3k64_dev_kernel<1>(stamp, abl != 0);
+    };
+    if (abl) KV_HIP(lds_opt_in((const void*)r3kern(false), bytes));
+    auto launch = [&]() -> int {  // the product's launch, or the ablated kernel on the same grid
+        if (!abl) return i8f32_gemm<K>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, false, 0, r3, share);
+        hipLaunchKernelGGL(r3kern(false), dim3(nwg), dim3(512), bytes, 0, v8.p, ev.p, u8.p, eu.p, m.p, rows, 512, rows,
+                           nullptr);
+        KV_HIP(hipGetLastError());
+        return KV_OK;
+    };
     int rc;
     for (int w = 0; w < 3; ++w)
-        if ((rc = i8f32_gemm<K>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, false, 0, r3))) return rc;
+        if ((rc = launch())) return rc;
     KV_HIP(hipDeviceSynchronize());
     kv::DevEvent e0, e1;
     KV_HIP(e0.create());
@@ -2793,7 +2925,7 @@ int kv_dev_gemm_clock(int device, int rows, int digits, double seconds, double* 
     KV_HIP(hipEventRecord(e0.e, 0));
     while (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() < seconds) {
         for (int i = 0; i < 50; ++i)  // 50 launches queued per check (~25 ms at C3)
-            if ((rc = i8f32_gemm<K>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, false, 0, r3))) return rc;
+            if ((rc = launch())) return rc;
         launches += 50;
         KV_HIP(hipStreamSynchronize(0));
     }
@@ -2802,16 +2934,8 @@ int kv_dev_gemm_clock(int device, int rows, int digits, double seconds, double* 
     float ms = 0.f;
     KV_HIP(hipEventElapsedTime(&ms, e0.e, e1.e));
     // the stamped build, right after the loop (the chip still at the clock the loop held)
-    using T = kv::Wino88iTile<kv::kI8DigitsF32>;
-    const int tpw = i8f32_tiles_per_wg(rows) >= 4 ? i8f32_tiles_per_wg(rows) : 1;
-    const int tiles = kv::W88_XI * (rows / T::WM) * (512 / T::WN), nwg = tiles / tpw;
-    KV_REQUIRE(tiles % (8 * tpw) == 0, KV_EINVAL, "kv_dev_gemm_clock: %d tiles, %d per workgroup", tiles, tpw);
     KV_HIP(stamps.alloc((size_t)nwg * 4));
-    // the stamped build of the form the product launches (R3: the 64-k-stage kernel)
-    const int bytes = r3 ? 3 * 4 * 128 * 96 + 2 * tpw * 1024 : KV_I8F32_NB * T::STAGE;
-    auto kern = r3 ? (tpw == 5   ? kv::wino88i32_gemm_r3k64_kernel<K, 5, true>
-                      : tpw == 4 ? kv::wino88i32_gemm_r3k64_kernel<K, 4, true>
-                                 : kv::wino88i32_gemm_r3k64_kernel<K, 1, true>)
+    auto kern = r3 ? r3kern(true)
                    : (tpw == 5   ? kv::wino88i32_gemm_lagt_kernel<K, 5, KV_I8F32_LJ, true, 4, KV_I8F32_NB>
                       : tpw == 4 ? kv::wino88i32_gemm_lagt_kernel<K, 4, KV_I8F32_LJ, true, 4, KV_I8F32_NB>
                                  : kv::wino88i32_gemm_lagt_kernel<K, 1, KV_I8F32_LJ, true, 4, KV_I8F32_NB>);
@@ -2834,7 +2958,21 @@ int kv_dev_gemm_clock(int device, int rows, int digits, double seconds, double* 
     out[1] = 1000.0 * ms / launches;
     out[2] = launches;
     out[3] = tpw;
+    out[4] = nwg;
     return KV_OK;
+}
+
+extern "C" {
+
+int kv_dev_gemm_clock(int device, int rows, int digits, double seconds, double* out) {
+    double o[5];
+    const int rc = gemm_clock(device, rows, digits, 0, 1, seconds, out ? o : nullptr);
+    if (!rc) memcpy(out, o, 4 * sizeof(double));  // this entry's out holds 4
+    return rc;
+}
+
+int kv_dev_r3gemm_clock(int device, int rows, int abl, int share, double seconds, double* out) {
+    return gemm_clock(device, rows, 3, abl, share, seconds, out);
 }
 
 // Phase timing of the fp32 tower's held-V output kernel (a diagnostic build: wino88i32_out_kernel<., ., 512, R3,

@@ -1013,8 +1013,15 @@ __device__ __forceinline__ i32x16_t r3mfma(i8x16_t a, i8x16_t b, i32x16_t c) {
 // B digit 0 (6), and chunk 1's B digits 1-2 (6) after the next barrier under that stage's first reads. Same
 // products, same exact int32 levels, same bits as the 32-k lagt form it replaced (measured bit-identical,
 // profiles/r06_r3k64_ab.log; that form read 128-byte lines with a zero 4th slot and was retired with them).
+// A tile's last stage (more than one tile per workgroup) has nothing to lag: it runs column half 0's MFMAs first,
+// chunk 1's B digits 1-2 included, and half 0's epilogue (the exact three-level combine, one rounding, 16 stores)
+// between half 1's last 9 MFMAs, placed by sched_group_barrier; half 1's epilogue follows the stage. The
+// epilogue's stores address a wave-uniform 64-bit tile base plus a 32-bit lane offset. Exposed epilogue (the kernel
+// against ABL 16): 66 of 346 us at 2,048 rows before this, profiles/r3_gemm_epilogue_ab.log.
 // ABL (timing ablations, outputs invalid; never the product's): 1 no copies after the prologue, 2 no MFMAs (the
-// fragments still read), 4 no M stores, 8 no exponent loads in the epilogue. KV_R3_M_NT (1): M stored non-temporally -- the GEMM 339 -> 325 us, the
+// fragments still read), 4 no M stores, 8 no exponent loads in the epilogue, 16 no epilogue at all (the
+// accumulators consumed by an opaque use; kv_dev_r3gemm_clock only). With 4 or 16 the waits allow no M stores in
+// flight. KV_R3_M_NT (1): M stored non-temporally -- the GEMM 339 -> 325 us, the
 // output kernels that read it +2 %, forward -1.5 % at 2,048 boards, neutral at 256 (profiles/r06_mnt_ab.log).
 #ifndef KV_R3_M_NT
 #define KV_R3_M_NT 1
@@ -1037,6 +1044,11 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
     constexpr int PLANE = 128 * 96, STAGE = 4 * PLANE;  // [operand][chunk] planes: 48 KiB
     static_assert(NK % 2 == 0 && NU > PD && 8 * GL * 1024 == STAGE, "64-k stages, 6 pieces per wave");
     constexpr double kStep = 0.00390625;  // level weight: radix 256
+    // SPLIT: a tile's last stage finishes column half 0 first and runs that half's epilogue between half 1's last
+    // MFMAs (below). Not with one tile per workgroup: that form gains nothing from it (its two workgroups per CU
+    // run out of step already) and the compiler spills registers there
+    constexpr bool SPLIT = TPW > 1;
+    constexpr int MST = (ABL & (4 | 16)) ? 0 : 32;  // M stores a tile's epilogue leaves in flight (none: ablated)
 
     extern __shared__ __attribute__((aligned(16))) i8x16_t lds_i8k64[];
     char* const L0 = (char*)lds_i8k64;
@@ -1095,6 +1107,7 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
     };
 
     const int lr = lane & 31, lh = lane >> 5;
+    const unsigned mlo = (unsigned)(4 * lh * cout + lr) * 4u;  // this lane's byte in its wave's block of an M tile
     const int arow = wm * 32 + lr;
     int aoff[2][ND], boff[2][NT][ND];
 #pragma unroll
@@ -1160,14 +1173,38 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
                     for (int nt = 0; nt < NT; ++nt)
                         acc[i + jb][nt] = r3mfma<ABL>(pa[i], pb[jb - 1][nt], acc[i + jb][nt]);
         };
+        // M addresses: one wave-uniform 64-bit base per tile plus this lane's unsigned 32-bit byte offset mlo inside
+        // the wave's 32 x 64 block (< 128 cout 4 = 256 KiB); a row or column half of the block is a wave-uniform
+        // step from the base -- no per-store 64-bit row * cout multiply
+        float* const Mt = M + ((size_t)xis[j] * stride + rbs[j] + wu / WC * 32) * cout + nbs[j] + wu % WC * NT * 32;
+        const int* const evx = exg + j * 256 + wm * 32;  // LDS (staged below)
+        auto epi = [&](int nt) {  // column half nt of the tile: the three levels combined (exact), one rounding
+            const int ec = (ABL & 8) ? -14 : exg[j * 256 + 128 + wn * NT * 32 + nt * 32 + lr] - 14;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rowu = (r & 3) + 8 * (r >> 2), row = rowu + 4 * lh;
+                double mm = (double)acc[ND - 1][nt][r];
+#pragma unroll
+                for (int l = ND - 2; l >= 0; --l) mm = __builtin_fma(mm, kStep, (double)acc[l][nt][r]);  // exact
+                const float o = (float)ldexp(mm, ((ABL & 8) ? 0 : evx[row]) + ec);
+                float* const mp = (float*)((char*)(Mt + (size_t)rowu * cout + nt * 32) + mlo);
+                if constexpr ((ABL & 4) != 0)
+                    asm volatile("" ::"v"(o));
+                else if constexpr (KV_R3_M_NT)
+                    __builtin_nontemporal_store(o, mp);
+                else
+                    *mp = o;
+            }
+        };
         for (int ku = 0; ku < NU; ++ku) {
             const int s = j * NU + ku, sg = gi * NSG + s;
+            const bool last = SPLIT && ku == NU - 1;
             // stage sg's pieces landed (vmcnt counts in issue order): what may stay outstanding is the m later
             // stages already issued and, for a tile's first PD stages, the previous tile's 32 M stores
             const int m = NST - 1 - sg < PD - 1 ? NST - 1 - sg : PD - 1;
-            if ((gi > 0 || j > 0) && ku < PD) {
-                if (m == 0) vm_lgkm_wait<32>();
-                else vm_lgkm_wait<GL + 32>();
+            if (MST && (gi > 0 || j > 0) && ku < PD) {
+                if (m == 0) vm_lgkm_wait<MST>();
+                else vm_lgkm_wait<GL + MST>();
             } else {
                 if (m == 0) vm_lgkm_wait<0>();
                 else vm_lgkm_wait<GL>();
@@ -1203,7 +1240,7 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
 #pragma unroll
                 for (int i = 0; i + jb < ND; ++i)
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
+                    for (int nt = 0; nt < (last && jb > 0 ? 1 : NT); ++nt)  // last: nt 1's come below
                         acc[i + jb][nt] = r3mfma<ABL>(a0[i], b0[jb][nt], acc[i + jb][nt]);
                 if (jb == 0 && sg + PD < NST) {
                     issue1(3, s + PD, sg + PD);
@@ -1218,17 +1255,53 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
                 b1[2][nt] = *(const i8x16_t*)(buf + boff[1][nt][2]);
             }
             __builtin_amdgcn_sched_barrier(0);
+            if (last) {
+                // the tile's last stage: column half 0 finishes first (chunk 1's B digit 0 and, nothing left to lag
+                // behind a barrier, its digits 1-2), then its 16 values are combined, rounded and stored between
+                // column half 1's 9 remaining MFMAs (chunk 0's B digits 1-2, chunk 1's three) -- the matrix pipe
+                // runs under half of the epilogue's VALU work instead of idling through all of it. Same products
+                // into the same exact int32 levels, so the same bits; every store still issues before the next
+                // tile's first wait, so no wait count changes
 #pragma unroll
-            for (int i = 0; i < ND; ++i)
+                for (int i = 0; i < ND; ++i) acc[i][0] = r3mfma<ABL>(a1[i], b1[0][0], acc[i][0]);
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[i][nt] = r3mfma<ABL>(a1[i], b1[0][nt], acc[i][nt]);
-            pa[0] = a1[0];
-            pa[1] = a1[1];
+                for (int jb = 1; jb < ND; ++jb)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                pb[0][nt] = b1[1][nt];
-                pb[1][nt] = b1[2][nt];
+                    for (int i = 0; i + jb < ND; ++i) acc[i + jb][0] = r3mfma<ABL>(a1[i], b1[jb][0], acc[i + jb][0]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int jb = 1; jb < ND; ++jb)
+#pragma unroll
+                    for (int i = 0; i + jb < ND; ++i) acc[i + jb][1] = r3mfma<ABL>(a0[i], b0[jb][1], acc[i + jb][1]);
+#pragma unroll
+                for (int i = 0; i < ND; ++i) acc[i][1] = r3mfma<ABL>(a1[i], b1[0][1], acc[i][1]);
+#pragma unroll
+                for (int jb = 1; jb < ND; ++jb)
+#pragma unroll
+                    for (int i = 0; i + jb < ND; ++i) acc[i + jb][1] = r3mfma<ABL>(a1[i], b1[jb][1], acc[i + jb][1]);
+                if constexpr ((ABL & (2 | 16)) == 0) {
+                    epi(0);
+#pragma unroll
+                    for (int q = 0; q < 9; ++q) {  // per MFMA: 16 VALU issues (two values' worth), two of the 16 stores
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x002, 16, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x040, 2, 0);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            } else {
+#pragma unroll
+                for (int i = 0; i < ND; ++i)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt)
+                        acc[i][nt] = r3mfma<ABL>(a1[i], b1[0][nt], acc[i][nt]);
+                pa[0] = a1[0];
+                pa[1] = a1[1];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    pb[0][nt] = b1[1][nt];
+                    pb[1][nt] = b1[2][nt];
+                }
             }
             if (j == 0 && ku == 1) {  // the group's exponents (read back after the next barrier)
 #pragma unroll
@@ -1236,27 +1309,15 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
                     if (tid + q * 512 < TPW * 256) exg[tid + q * 512] = exv[q];
             }
         }
-        h2();
-        const int xi = xis[j], n_base = nbs[j], r_base = rbs[j];
-        const int* evx = exg + j * 256 + wm * 32;  // LDS (staged above)
+        if constexpr (!SPLIT) h2();
+        if constexpr ((ABL & 16) != 0) {  // ablation: no epilogue, the accumulators consumed by an opaque use
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int col = n_base + wn * NT * 32 + nt * 32 + lr;
-            const int ec = (ABL & 8) ? -14 : exg[j * 256 + 128 + wn * NT * 32 + nt * 32 + lr] - 14;
+            for (int l = 0; l < ND; ++l)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                double mm = (double)acc[ND - 1][nt][r];
-#pragma unroll
-                for (int l = ND - 2; l >= 0; --l) mm = __builtin_fma(mm, kStep, (double)acc[l][nt][r]);  // exact
-                const float o = (float)ldexp(mm, ((ABL & 8) ? 0 : evx[row]) + ec);
-                if constexpr ((ABL & 4) != 0)
-                    asm volatile("" ::"v"(o));
-                else if constexpr (KV_R3_M_NT)
-                    __builtin_nontemporal_store(o, &M[((size_t)xi * stride + r_base + wm * 32 + row) * cout + col]);
-                else
-                    M[((size_t)xi * stride + r_base + wm * 32 + row) * cout + col] = o;
-            }
+                for (int nt = 0; nt < NT; ++nt) asm volatile("" ::"v"(acc[l][nt]));
+        } else {
+            if constexpr (!SPLIT || (ABL & 2) != 0) epi(0);
+            epi(1);
         }
     }
     }  // groups

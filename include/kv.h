@@ -464,6 +464,17 @@ int kv_dev_valid_moves(int device, const int8_t* states, int n, uint16_t* moves_
 int kv_dev_attacks(int device, const int8_t* states, int n, uint64_t* attacked);
 /* makeMove (chessEngine.py:127-197) of move index[i] of each state's list. */
 int kv_dev_make_move(int device, int8_t* states, const int* index, int n);
+/* Where the engine's games start (tests only: self-play and the arena have no opening book). states: n >= 1
+ * 80-byte state vectors as kv_search takes them, checked as kv_search checks them (KV_EINVAL and a reason in
+ * kv_last_error()). The game with global id g starts from states[g % n], at ply 0 with a fresh slot, whether
+ * it is one of the first wave of games or starts in a recycled slot, in both seed modes -- so which position a
+ * game gets depends on its id alone, not on slots, recycling order, game_id_base or game_id_stride. NULL with
+ * n 0 restores the initial position. Only on an engine that has neither run nor searched (later: KV_EINVAL);
+ * the games the engine's creation already started are re-seated. A start without a legal move is a game of 0
+ * plies (no record, no root-visit row, reason 2 or 3); a kings-only start plays one move and is then a
+ * reason-4 draw, as the reference tests isDraw only after a move. With no starts set nothing of the engine
+ * changes. */
+int kv_dev_set_starts(kv_engine* e, const int8_t* states /*[n][80]*/, int n);
 /* numpy RandomState(seed[i]).dirichlet([alpha]*k) `draws` times per stream:
  * out [n][draws][k] fp64, attempts [n][draws] gamma attempts consumed,
  * tail [n] = the stream's next random_sample() after the draws. */

@@ -84,6 +84,10 @@ struct DevCfg {
     int sims;             // 0: reference move selection; >0: PUCT search
     int eval_mode;        // KV_EVAL_*
     int sample_plies;     // MCTS move choice: 0 every ply drawn, k > 0 first maximum from ply k on, -1 on every ply
+    // kv_dev_set_starts (test-only; nullptr: every game starts from the initial position): n_starts 80-byte
+    // state vectors, the game with global id g starts from starts[g % n_starts]
+    const int8_t* starts;
+    int n_starts;
 };
 
 __device__ inline Pos slot_pos(const Slot& s, const int8_t* board) {

@@ -39,12 +39,29 @@ __constant__ const int8_t kStart[64] = {9, 11, 10, 8, 7, 10, 11, 9, 12, 12, 12, 
                                         0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
                                         6, 6, 6, 6, 6, 6, 6, 6, 3, 5, 4, 2, 1, 4, 5, 3};
 
+// kv_dev_set_starts: the state vector game gid starts from, nullptr for the initial position
+__device__ inline const int8_t* start_vec(const DevCfg& cfg, long long gid) {
+    if (!cfg.starts) return nullptr;
+    const long long r = gid % cfg.n_starts;
+    return cfg.starts + (size_t)(r < 0 ? r + cfg.n_starts : r) * 80;
+}
+
+// the position fields of a slot from a state vector (as k_search_load reads one)
+__device__ inline void start_pos_fields(Slot& s, const int8_t* v) {
+    s.wtm = v[64];
+    s.wkr = v[65]; s.wkc = v[66]; s.bkr = v[67]; s.bkc = v[68];
+    s.flags = (v[69] ? F_WKM : 0) | (v[70] ? F_BKM : 0) | (v[71] ? F_WRK : 0) | (v[72] ? F_WRQ : 0) |
+              (v[73] ? F_BRK : 0) | (v[74] ? F_BRQ : 0);
+    s.ep = v[75] < 0 ? -1 : v[75] * 8 + v[76];
+}
+
 // GameState() :34-84: the slot fields of a new game (board and streams set by the caller)
 __device__ void start_game_fields(const DevCfg& cfg, Slot& s, long long gid) {
     s.game_id = gid;
     s.status = ST_ACTIVE;
     s.ply = 0;
     s.wtm = 1; s.wkr = 7; s.wkc = 4; s.bkr = 0; s.bkc = 4; s.flags = 0; s.ep = -1;
+    if (const int8_t* v = start_vec(cfg, gid)) start_pos_fields(s, v);
     s.nmoves = 0;
     s.buf = 0;
     s.consumed = 0;
@@ -62,7 +79,8 @@ __device__ void start_game_fields(const DevCfg& cfg, Slot& s, long long gid) {
 __device__ void start_game(const DevCfg& cfg, Slot& s, int8_t* board, uint32_t* np_mt, uint32_t* py_mt,
                            long long k) {
     const long long gid = cfg.id_base + k * cfg.id_stride;
-    for (int i = 0; i < 64; ++i) board[i] = kStart[i];
+    const int8_t* v = start_vec(cfg, gid);
+    for (int i = 0; i < 64; ++i) board[i] = v ? v[i] : kStart[i];
     start_game_fields(cfg, s, gid);
     if (cfg.seed_mode == KV_SEED_PER_GAME) {
         const unsigned long long sd = cfg.seed + (unsigned long long)gid;
@@ -87,6 +105,19 @@ __global__ void k_init(DevCfg cfg, Slot* slots, int8_t* boards, uint32_t* np_mt,
         start_game(cfg, s, boards + (size_t)i * 64, np_mt + (size_t)i * MT_WORDS, py_mt + (size_t)i * MT_WORDS, i);
         atomicAdd(&ctr->active, 1);
     }
+    slots[i] = s;
+}
+
+// kv_dev_set_starts on a fresh engine: the games k_init started take their start positions (or the initial
+// one again); everything else of the slot is as k_init left it
+__global__ void k_set_starts(DevCfg cfg, Slot* slots, int8_t* boards) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cfg.slots || (long long)i >= cfg.n_games) return;
+    Slot s = slots[i];
+    const int8_t* v = start_vec(cfg, s.game_id);
+    for (int q = 0; q < 64; ++q) boards[(size_t)i * 64 + q] = v ? v[q] : kStart[q];
+    s.wtm = 1; s.wkr = 7; s.wkc = 4; s.bkr = 0; s.bkc = 4; s.flags = 0; s.ep = -1;
+    if (v) start_pos_fields(s, v);
     slots[i] = s;
 }
 
@@ -306,7 +337,8 @@ __global__ __launch_bounds__(128) void k_finish(DevCfg cfg, Slot* slots, int8_t*
         s.status = ST_IDLE;
     }
     if (k >= 0) {  // the slot starts game k: board + numpy stream by wave 0, fields by thread 0
-        board[lane] = kStart[lane];
+        const int8_t* v = start_vec(cfg, gid);
+        board[lane] = v ? v[lane] : kStart[lane];
         if (cfg.seed_mode == KV_SEED_PER_GAME) wave_seed_genrand(np_mt + (size_t)i * MT_WORDS, (uint32_t)sd, lane);
         if (tid == 0) start_game_fields(cfg, s, gid);
     }
@@ -677,6 +709,7 @@ struct kv_engine {
     bool ec_claims_out = false;
     // kv_search: an engine serves either kv_run or kv_search (used: 0 neither yet, 1 kv_run, 2 kv_search)
     int used = 0;
+    int8_t* starts = nullptr;  // kv_dev_set_starts: [n_starts][80] on the device (dc.starts), nullptr: none set
     kv::SearchWs sw = {};
     size_t sw_rows = 0;           // rows (positions x leaves) the leaf workspaces hold
     int8_t* s_states = nullptr;   // [slots][80]
@@ -862,6 +895,8 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     d.sims = cfg->sims;
     d.eval_mode = cfg->eval_mode;
     d.sample_plies = cfg->sample_plies;
+    d.starts = nullptr;
+    d.n_starts = 0;
     e->leaves = std::max(cfg->leaves, 1);
     e->big = e->leaves > 1 ? (long long)cfg->slots * e->leaves > 16 : cfg->slots > 16;
     // several leaves in the > 16-row class: a root batch of fewer than 17 slots is padded to 17 rows (empty boards)
@@ -1110,6 +1145,44 @@ int kv_set_max_moves(kv_engine* e, int max_moves) {
     KV_REQUIRE(e, KV_EINVAL, "kv_set_max_moves: NULL");
     e->cfg.max_moves = max_moves;
     e->dc.max_moves = max_moves;
+    return KV_OK;
+}
+
+// test-only (kv.h): where the engine's games start. The vectors are checked as kv_search checks its positions
+int kv_dev_set_starts(kv_engine* e, const int8_t* states, int n) {
+    KV_REQUIRE(e, KV_EINVAL, "kv_dev_set_starts: NULL engine");
+    KV_REQUIRE(e->used == 0, KV_EINVAL,
+               "kv_dev_set_starts: this engine has %s; the starts are set on a fresh engine only",
+               e->used == 1 ? "run self-play (kv_run)" : "searched positions (kv_search)");
+    KV_REQUIRE(states ? n >= 1 : n == 0, KV_EINVAL,
+               "kv_dev_set_starts: %d states with %s (at least 1 with states; NULL and 0 restore the initial position)",
+               n, states ? "a pointer" : "NULL");
+    for (int i = 0; i < n; ++i) {
+        const int8_t* v = states + (size_t)i * 80;
+        bool ok = (v[64] == 0 || v[64] == 1) && v[75] >= -1 && v[75] < 8 && v[76] >= -1 && v[76] < 8 &&
+                  (v[75] < 0) == (v[76] < 0);
+        for (int q = 0; q < 64; ++q) ok = ok && v[q] >= 0 && v[q] <= 12;
+        for (int q = 65; q < 69; ++q) ok = ok && v[q] >= 0 && v[q] < 8;
+        KV_REQUIRE(ok, KV_EINVAL, "kv_dev_set_starts: position %d is not a state vector (codes 0..12, wtm 0/1, king "
+                   "squares 0..7, ep -1..7)", i);
+    }
+    KV_HIP(hipSetDevice(e->cfg.device));
+    KV_HIP(hipStreamSynchronize(e->st));
+    if (e->starts) KV_HIP(hipFree(e->starts));
+    e->starts = nullptr;
+    e->dc.starts = nullptr;
+    e->dc.n_starts = 0;
+    if (n > 0) {
+        KV_HIP(hipMalloc((void**)&e->starts, (size_t)n * 80));
+        KV_HIP(hipMemcpy(e->starts, states, (size_t)n * 80, hipMemcpyHostToDevice));
+        e->dc.starts = e->starts;
+        e->dc.n_starts = n;
+    }
+    // the games k_init started are re-seated
+    hipLaunchKernelGGL(kv::k_set_starts, dim3((e->cfg.slots + 63) / 64), dim3(64), 0, e->st, e->dc, e->slots,
+                       e->boards);
+    KV_HIP(hipGetLastError());
+    KV_HIP(hipStreamSynchronize(e->st));
     return KV_OK;
 }
 
@@ -2144,7 +2217,7 @@ void kv_destroy(kv_engine* e) {
                     e->lf_moves[0], e->lf_moves[1], e->lf_cnt[0], e->lf_cnt[1], e->lf_logits[0], e->lf_logits[1],
                     e->lf_values[0], e->lf_values[1], e->lf_hlogits, e->lf_ctr,
                     e->ec_tab[0].ent, e->ec_tab[0].claim, e->ec_tab[1].ent, e->ec_tab[1].claim, e->ec_hit, e->ec_idx,
-                    e->ec_ctr};
+                    e->ec_ctr, e->starts};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (e->ctr_host) (void)hipHostFree(e->ctr_host);

@@ -112,6 +112,16 @@ class SelfPlayEngine:
     def set_max_moves(self, max_moves):
         _lib.check(_lib.lib().kv_set_max_moves(self.h, max_moves if max_moves else 0), "kv_set_max_moves")
 
+    def _set_starts(self, states):
+        """Test-only (kv_dev_set_starts): game g starts from states[g % n] ([n, 80] int8 state vectors); None
+        restores the initial position. Only before the first run()."""
+        if states is None:
+            _lib.check(_lib.lib().kv_dev_set_starts(self.h, None, 0), "kv_dev_set_starts")
+            return
+        st = np.ascontiguousarray(states, dtype=np.int8).reshape(-1, 80)
+        _lib.check(_lib.lib().kv_dev_set_starts(self.h, st.ctypes.data_as(C.POINTER(C.c_int8)), len(st)),
+                   "kv_dev_set_starts")
+
     def reset_records(self):
         _lib.check(_lib.lib().kv_reset_records(self.h), "kv_reset_records")
 

@@ -667,11 +667,13 @@ static void eval_buffer(kvo_eval_fn cb, void* ctx, float* buf, int n, kvo_last* 
 /* _run_single_game :111-255. np_mt / py_mt are the numpy and CPython streams;
  * `last` is the function attribute _run_single_game._last_outputs. Records:
  * states (80 B each) and move indices; returns plies. */
-int kvo_play_game(const kvo_game_cfg* cfg, MT* np_mt, MT* py_mt, kvo_eval_fn cb, kvo_softmax_fn smx, void* ctx,
-                  kvo_last* last, int8_t* rec_states, uint16_t* rec_moves, int cap, int* eval_sizes, int size_cap,
-                  kvo_game_result* res) {
+/* kvo_play_game from a given start (an 80-byte state vector; NULL: the initial position) */
+int kvo_play_game_from(const kvo_game_cfg* cfg, const int8_t* start, MT* np_mt, MT* py_mt, kvo_eval_fn cb,
+                       kvo_softmax_fn smx, void* ctx, kvo_last* last, int8_t* rec_states, uint16_t* rec_moves, int cap,
+                       int* eval_sizes, int size_cap, kvo_game_result* res) {
     GS g;
-    gs_init(&g);
+    if (start) gs_from_vec(&g, start);
+    else gs_init(&g);
     static ML ml;
     float* buf = (float*)malloc(sizeof(float) * 768 * (size_t)(cfg->batch > 0 ? cfg->batch : 1));
     float probs[4096];
@@ -753,6 +755,13 @@ int kvo_play_game(const kvo_game_cfg* cfg, MT* np_mt, MT* py_mt, kvo_eval_fn cb,
     return move_count;
 }
 
+int kvo_play_game(const kvo_game_cfg* cfg, MT* np_mt, MT* py_mt, kvo_eval_fn cb, kvo_softmax_fn smx, void* ctx,
+                  kvo_last* last, int8_t* rec_states, uint16_t* rec_moves, int cap, int* eval_sizes, int size_cap,
+                  kvo_game_result* res) {
+    return kvo_play_game_from(cfg, NULL, np_mt, py_mt, cb, smx, ctx, last, rec_states, rec_moves, cap, eval_sizes,
+                              size_cap, res);
+}
+
 /* expose struct sizes so the ctypes wrapper can allocate opaque blobs */
 int kvo_sizeof_mt(void) { return (int)sizeof(MT); }
 int kvo_sizeof_last(void) { return (int)sizeof(kvo_last); }
@@ -774,6 +783,7 @@ typedef struct {
     int max_moves;
     double eps, alpha;
     int edge_cap; /* <= 0: KV_MAXM x (sims + 1) (kv_engine.hip kv_create), which cannot overflow */
+    int sample_plies; /* kv_config.sample_plies: 0 every move drawn, k > 0 the first maximum from ply k on, -1 always */
 } kvo_mcts_cfg;
 
 #define KVO_MAXM 320 /* include/kv.h KV_MAXM */
@@ -899,8 +909,8 @@ typedef struct {
     int maxm;
 } MG;
 
-static void mg_init(MG* m, const kvo_mcts_cfg* cfg, MT* np_mt, MT* py_mt, uint16_t* rec_moves, int cap,
-                    int32_t* visits, int maxm) {
+static void mg_init(MG* m, const kvo_mcts_cfg* cfg, const int8_t* start, MT* np_mt, MT* py_mt, uint16_t* rec_moves,
+                    int cap, int32_t* visits, int maxm) {
     memset(m, 0, sizeof *m);
     m->cfg = cfg; m->np_mt = np_mt; m->py_mt = py_mt;
     m->S = cfg->sims; m->ncap = m->S + 2;
@@ -927,7 +937,8 @@ static void mg_init(MG* m, const kvo_mcts_cfg* cfg, MT* np_mt, MT* py_mt, uint16
     m->lm = (ML*)malloc(sizeof(ML));
     m->reason = -1;
     m->rec_moves = rec_moves; m->cap = cap; m->visits = visits; m->maxm = maxm;
-    gs_init(&m->g);
+    if (start) gs_from_vec(&m->g, start);
+    else gs_init(&m->g);
 }
 
 static void mg_free(MG* m) {
@@ -1046,7 +1057,14 @@ static void mg_commit(MG* m) {
     if (m->visits && m->move_count < m->cap)
         for (int j = 0; j < m->maxm; ++j)
             m->visits[(size_t)m->move_count * m->maxm + j] = j < ml->n ? m->e_N[j] : -1;
-    const int pick = choose_weighted_c(m->py_mt, m->w, ml->n);
+    const int sp = m->cfg->sample_plies;
+    int pick = 0;
+    if (sp == 0 || (sp > 0 && m->move_count < sp)) {
+        pick = choose_weighted_c(m->py_mt, m->w, ml->n);
+    } else { /* the first maximum of the visit counts; the CPython stream is not advanced */
+        for (int i = 1; i < ml->n; ++i)
+            if (m->e_N[i] > m->e_N[pick]) pick = i;
+    }
     const Mv mv = ml->m[pick];
     if (m->move_count < m->cap) m->rec_moves[m->move_count] = (uint16_t)((mv.fr * 8 + mv.fc) * 64 + mv.tr * 8 + mv.tc);
     make_move(&m->g, &mv);
@@ -1102,8 +1120,10 @@ static void mg_eval(MG* const* want, const GS* const* pos, int n, kvo_eval_fn cb
  * and (visits != NULL) visits + k*cap*maxm, and res[k]. Each game's search is
  * the single-game one exactly (the batch only groups the network calls).
  * Returns 0, or -1 when some expansion did not fit its edge pool. */
-int kvo_mcts_play_batch(const kvo_mcts_cfg* cfg, int G, MT** np_mts, MT** py_mts, kvo_eval_fn cb, void* ctx,
-                        uint16_t* rec_moves, int cap, int32_t* visits, int maxm, kvo_game_result* res) {
+/* starts: NULL, or G 80-byte state vectors, game k's start position */
+int kvo_mcts_play_batch_from(const kvo_mcts_cfg* cfg, int G, const int8_t* starts, MT** np_mts, MT** py_mts,
+                             kvo_eval_fn cb, void* ctx, uint16_t* rec_moves, int cap, int32_t* visits, int maxm,
+                             kvo_game_result* res) {
     MG* gm = (MG*)malloc(sizeof(MG) * (size_t)G);
     MG** want = (MG**)malloc(sizeof(MG*) * (size_t)G);
     const GS** pos = (const GS**)malloc(sizeof(GS*) * (size_t)G);
@@ -1111,7 +1131,8 @@ int kvo_mcts_play_batch(const kvo_mcts_cfg* cfg, int G, MT** np_mts, MT** py_mts
     float* lg = (float*)malloc(sizeof(float) * 4096 * (size_t)G);
     float* val = (float*)malloc(sizeof(float) * (size_t)G);
     for (int k = 0; k < G; ++k)
-        mg_init(&gm[k], cfg, np_mts[k], py_mts[k], rec_moves + (size_t)k * cap, cap,
+        mg_init(&gm[k], cfg, starts ? starts + (size_t)k * 80 : NULL, np_mts[k], py_mts[k],
+                rec_moves + (size_t)k * cap, cap,
                 visits ? visits + (size_t)k * cap * maxm : NULL, maxm);
     for (;;) {
         int n = 0;
@@ -1144,6 +1165,11 @@ int kvo_mcts_play_batch(const kvo_mcts_cfg* cfg, int G, MT** np_mts, MT** py_mts
     return overflow ? -1 : 0;
 }
 
+int kvo_mcts_play_batch(const kvo_mcts_cfg* cfg, int G, MT** np_mts, MT** py_mts, kvo_eval_fn cb, void* ctx,
+                        uint16_t* rec_moves, int cap, int32_t* visits, int maxm, kvo_game_result* res) {
+    return kvo_mcts_play_batch_from(cfg, G, NULL, np_mts, py_mts, cb, ctx, rec_moves, cap, visits, maxm, res);
+}
+
 /* plays one game; rec_moves[ply], visits[ply * maxm + j] = root visit counts
  * in root move-list order (maxm entries per ply, -1 padded). Returns the
  * number of plies, or -1 when an expansion did not fit the edge pool (the
@@ -1151,5 +1177,11 @@ int kvo_mcts_play_batch(const kvo_mcts_cfg* cfg, int G, MT** np_mts, MT** py_mts
 int kvo_mcts_play_game(const kvo_mcts_cfg* cfg, MT* np_mt, MT* py_mt, kvo_eval_fn cb, void* ctx,
                        uint16_t* rec_moves, int cap, int32_t* visits, int maxm, kvo_game_result* res) {
     const int rc = kvo_mcts_play_batch(cfg, 1, &np_mt, &py_mt, cb, ctx, rec_moves, cap, visits, maxm, res);
+    return rc < 0 ? -1 : res->plies;
+}
+
+int kvo_mcts_play_game_from(const kvo_mcts_cfg* cfg, const int8_t* start, MT* np_mt, MT* py_mt, kvo_eval_fn cb,
+                            void* ctx, uint16_t* rec_moves, int cap, int32_t* visits, int maxm, kvo_game_result* res) {
+    const int rc = kvo_mcts_play_batch_from(cfg, 1, start, &np_mt, &py_mt, cb, ctx, rec_moves, cap, visits, maxm, res);
     return rc < 0 ? -1 : res->plies;
 }

@@ -63,6 +63,7 @@ def lib():
         L.kvo_play_game.argtypes = [C.POINTER(GameCfg), C.c_void_p, C.c_void_p, EVAL_FN, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.POINTER(C.c_int8), C.POINTER(C.c_uint16), C.c_int,
                                     C.POINTER(C.c_int), C.c_int, C.POINTER(GameResult)]
+        L.kvo_play_game_from.argtypes = [C.POINTER(GameCfg), C.POINTER(C.c_int8)] + L.kvo_play_game.argtypes[1:]
         _lib = L
     return _lib
 
@@ -146,8 +147,9 @@ class Last:
 
 
 def play_game(eval_fn, np_mt: MT, py_mt: MT, last: Last, max_moves=None, batch=16, eps=0.25, alpha=0.3,
-              softmax_fn=None, cap=4096):
+              softmax_fn=None, cap=4096, start=None):
     """Restated _run_single_game. eval_fn(planes[n,12,8,8]) -> (logits[n,4096], values[n]).
+    start: the 80-byte state vector the game starts from (None: the initial position).
     Returns dict(moves, states, result, eval_sizes)."""
 
     def _cb(ctx, planes, n, logits, values):
@@ -167,16 +169,17 @@ def play_game(eval_fn, np_mt: MT, py_mt: MT, last: Last, max_moves=None, batch=1
     moves = np.zeros(cap, dtype=np.uint16)
     sizes = np.zeros(cap, dtype=np.int32)
     res = GameResult()
-    n = lib().kvo_play_game(C.byref(cfg), np_mt.buf, py_mt.buf, cb, C.cast(smx, C.c_void_p) if smx else None, None,
-                            last.buf, _p(states, C.c_int8), _p(moves, C.c_uint16), cap, _p(sizes, C.c_int), cap,
-                            C.byref(res))
+    st0 = None if start is None else np.ascontiguousarray(start, dtype=np.int8).reshape(80)
+    n = lib().kvo_play_game_from(C.byref(cfg), None if st0 is None else _p(st0, C.c_int8), np_mt.buf, py_mt.buf, cb,
+                                 C.cast(smx, C.c_void_p) if smx else None, None, last.buf, _p(states, C.c_int8),
+                                 _p(moves, C.c_uint16), cap, _p(sizes, C.c_int), cap, C.byref(res))
     return dict(moves=moves[:n].copy(), states=states[:n].copy(), plies=res.plies, outcome=res.outcome,
                 reward=float(res.reward), reason=res.reason, eval_sizes=sizes[:res.n_evals].copy())
 
 
 class MctsCfg(C.Structure):
     _fields_ = [("sims", C.c_int), ("c_puct", C.c_float), ("max_moves", C.c_int), ("eps", C.c_double),
-                ("alpha", C.c_double), ("edge_cap", C.c_int)]
+                ("alpha", C.c_double), ("edge_cap", C.c_int), ("sample_plies", C.c_int)]
 
 
 class TreeOverflow(RuntimeError):
@@ -200,16 +203,17 @@ def softmax_det_4096(logits):
 
 
 def mcts_play_game(sims, np_mt: MT, py_mt: MT, eval_fn=None, max_moves=None, c_puct=1.5, eps=0.25, alpha=0.3,
-                   edge_cap=0, cap=2048, maxm=320):
+                   edge_cap=0, cap=2048, maxm=320, start=None, sample_plies=0):
     """Restated PUCT self-play game (build-defined semantics, kv_mcts.hip).
-    eval_fn None = hash test evaluator. Returns dict(moves, visits, ...);
+    eval_fn None = hash test evaluator. start: the 80-byte state vector the game starts from (None: the
+    initial position); sample_plies: kv_config.sample_plies. Returns dict(moves, visits, ...);
     raises TreeOverflow where the device raises KV_EOVERFLOW."""
     L = lib()
-    if not hasattr(L.kvo_mcts_play_game, "_sig"):
-        L.kvo_mcts_play_game.argtypes = [C.POINTER(MctsCfg), C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.POINTER(C.c_uint16), C.c_int, C.POINTER(C.c_int32), C.c_int,
-                                         C.POINTER(GameResult)]
-        L.kvo_mcts_play_game._sig = True
+    if not hasattr(L.kvo_mcts_play_game_from, "_sig"):
+        L.kvo_mcts_play_game_from.argtypes = [C.POINTER(MctsCfg), C.POINTER(C.c_int8), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_uint16), C.c_int,
+                                              C.POINTER(C.c_int32), C.c_int, C.POINTER(GameResult)]
+        L.kvo_mcts_play_game_from._sig = True
     cb = None
     if eval_fn is not None:
         def _cb(ctx, planes, n, logits, values):
@@ -218,12 +222,14 @@ def mcts_play_game(sims, np_mt: MT, py_mt: MT, eval_fn=None, max_moves=None, c_p
             np.ctypeslib.as_array(logits, shape=(n, 4096))[:] = lg
             np.ctypeslib.as_array(values, shape=(n,))[:] = np.asarray(vl).reshape(n)
         cb = EVAL_FN(_cb)
-    cfg = MctsCfg(sims, c_puct, max_moves if max_moves else 0, eps, alpha, int(edge_cap))
+    cfg = MctsCfg(sims, c_puct, max_moves if max_moves else 0, eps, alpha, int(edge_cap), int(sample_plies))
     moves = np.zeros(cap, dtype=np.uint16)
     visits = np.full((cap, maxm), -1, dtype=np.int32)
     res = GameResult()
-    n = L.kvo_mcts_play_game(C.byref(cfg), np_mt.buf, py_mt.buf, C.cast(cb, C.c_void_p) if cb else None,
-                             None, _p(moves, C.c_uint16), cap, _p(visits, C.c_int32), maxm, C.byref(res))
+    st0 = None if start is None else np.ascontiguousarray(start, dtype=np.int8).reshape(80)
+    n = L.kvo_mcts_play_game_from(C.byref(cfg), None if st0 is None else _p(st0, C.c_int8), np_mt.buf, py_mt.buf,
+                                  C.cast(cb, C.c_void_p) if cb else None, None, _p(moves, C.c_uint16), cap,
+                                  _p(visits, C.c_int32), maxm, C.byref(res))
     if n < 0:
         raise TreeOverflow(f"edge pool of {edge_cap} edges overflowed")
     return dict(moves=moves[:n].copy(), visits=visits[:n].copy(), plies=res.plies, outcome=res.outcome,
@@ -231,16 +237,18 @@ def mcts_play_game(sims, np_mt: MT, py_mt: MT, eval_fn=None, max_moves=None, c_p
 
 
 def mcts_play_batch(sims, seeds, eval_fn=None, max_moves=None, c_puct=1.5, eps=0.25, alpha=0.3, edge_cap=0,
-                    cap=2048, maxm=320, keep_visits=False):
-    """G restated PUCT games in lock-step (kvo_mcts_play_batch): game k seeded seeds[k] (both streams),
+                    cap=2048, maxm=320, keep_visits=False, starts=None, sample_plies=0):
+    """G restated PUCT games in lock-step (kvo_mcts_play_batch): game k seeded seeds[k] (both streams) and
+    started from starts[k] (80-byte state vectors; None: the initial position), sample_plies as kv_config's,
     every simulation's leaves that need the network evaluated as ONE eval_fn batch -- the device's batch
     shape. Each game equals mcts_play_game on its own seed. Returns a list of per-game dicts."""
     L = lib()
-    if not hasattr(L.kvo_mcts_play_batch, "_sig"):
-        L.kvo_mcts_play_batch.argtypes = [C.POINTER(MctsCfg), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_uint16), C.c_int,
-                                          C.POINTER(C.c_int32), C.c_int, C.POINTER(GameResult)]
-        L.kvo_mcts_play_batch._sig = True
+    if not hasattr(L.kvo_mcts_play_batch_from, "_sig"):
+        L.kvo_mcts_play_batch_from.argtypes = [C.POINTER(MctsCfg), C.c_int, C.POINTER(C.c_int8),
+                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                               C.POINTER(C.c_uint16), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                               C.POINTER(GameResult)]
+        L.kvo_mcts_play_batch_from._sig = True
     G = len(seeds)
     nps = [MT(int(s), "numpy") for s in seeds]
     pys = [MT(int(s), "python") for s in seeds]
@@ -254,13 +262,14 @@ def mcts_play_batch(sims, seeds, eval_fn=None, max_moves=None, c_puct=1.5, eps=0
             np.ctypeslib.as_array(logits, shape=(n, 4096))[:] = lg
             np.ctypeslib.as_array(values, shape=(n,))[:] = np.asarray(vl).reshape(n)
         cb = EVAL_FN(_cb)
-    cfg = MctsCfg(sims, c_puct, max_moves if max_moves else 0, eps, alpha, int(edge_cap))
+    cfg = MctsCfg(sims, c_puct, max_moves if max_moves else 0, eps, alpha, int(edge_cap), int(sample_plies))
+    st0 = None if starts is None else np.ascontiguousarray(starts, dtype=np.int8).reshape(G, 80)
     moves = np.zeros((G, cap), dtype=np.uint16)
     visits = np.full((G, cap, maxm), -1, dtype=np.int32) if keep_visits else None
     res = (GameResult * G)()
-    rc = L.kvo_mcts_play_batch(C.byref(cfg), G, np_arr, py_arr, C.cast(cb, C.c_void_p) if cb else None, None,
-                               _p(moves, C.c_uint16), cap, _p(visits, C.c_int32) if keep_visits else None, maxm,
-                               res)
+    rc = L.kvo_mcts_play_batch_from(C.byref(cfg), G, None if st0 is None else _p(st0, C.c_int8), np_arr, py_arr,
+                                    C.cast(cb, C.c_void_p) if cb else None, None, _p(moves, C.c_uint16), cap,
+                                    _p(visits, C.c_int32) if keep_visits else None, maxm, res)
     if rc < 0:
         raise TreeOverflow(f"edge pool of {edge_cap} edges overflowed")
     out = []

@@ -164,11 +164,13 @@ class CachedEval:
         return rows
 
 
-def play_many_cached(seeds, gids, sims, plies, leaves, cache_a, cache_b=None, **kw):
+def play_many_cached(seeds, gids, sims, plies, leaves, cache_a, cache_b=None, per_game=None, **kw):
     """tests/_mcts_selfplay_leaves.play_many for games that all start at ply-step 0 (no recycling, so list order
     is game order), the root batches through cache_x.roots and every step's batch through cache_x.leaves.
+    per_game: one dict of further SL.game keywords per game (its start position).
     -> (per-game outputs, dict(steps, pending: [A's, B's], batches: per sim-step the (A's, B's) pending rows))."""
-    gens = [SL.game(s, g, sims, n, leaves, **kw) for s, g, n in zip(seeds, gids, plies)]
+    per_game = per_game or [{}] * len(seeds)
+    gens = [SL.game(s, g, sims, n, leaves, **kw, **pg) for s, g, n, pg in zip(seeds, gids, plies, per_game)]
     ev = (cache_a, cache_b or cache_a)
     out, req = [None] * len(gens), {}
     info = dict(steps=0, pending=[0, 0], batches=[])

@@ -10,12 +10,14 @@ maximum of the root visit counts and the CPython stream is not advanced.
 Built from that file's node, the priors of tests/_mcts_search.py and the
 oracle's rules and streams. The game is a generator that yields (player, state
 after getValidMoves) per evaluation and is sent (logits[4096], value). It is
-told how many plies to play, so it restates no termination rule. Shared by
+told how many plies to play, or (plies=None) plays to the end by the rules of
+tests/_mcts_endings.py from any start position. Shared by
 tests/test_arena_cpu.py and tests/test_arena_gpu.py; not a test module itself."""
 import numpy as np
 
 from oracle import oracle as O
 
+from tests import _mcts_endings as E
 from tests import _mcts_search as S
 from tests._mcts_selfplay_reuse import _Node, hash_eval, leaf_priors, policy_index, root_priors
 
@@ -34,24 +36,32 @@ def player_of(gid, wtm):
     return A if ((gid % 2 == 0) == bool(wtm)) else B
 
 
-def game(seed, gid, sims, plies, sample_plies=0, c_puct=1.5, eps=0.0, alpha=0.3):
+def game(seed, gid, sims, plies, sample_plies=0, c_puct=1.5, eps=0.0, alpha=0.3, start=None, max_moves=None):
     """`plies` plies of the arena game with global id `gid` whose two streams are seeded `seed` (the engine's
     seed + gid), as a generator: yields (player, state) per evaluation, is sent (logits, value); returns one
     dict per ply: player, visits (root edge counts, list order), words (the root's move words), move (the
-    record's index from * 64 + to), sampled (the move was drawn)."""
+    record's index from * 64 + to), sampled (the move was drawn); the list's `extra` holds per ply board (the root's
+    64 codes as bytes), root_value and pending (the leaf rows the ply sent to the network). start: the state
+    vector the game starts from (None: the initial position). plies None: the game is played to its end under max_moves by
+    tests/_mcts_endings.py's rules and the list returned is an E.Played with result (plies, outcome, reason,
+    reward) and holds."""
     c = F(c_puct)
     np_mt, py_mt = O.MT(seed, "numpy"), O.MT(seed, "python")
     sqt = [F(np.sqrt(np.float64(k))) for k in range(sims + 4)]
-    vec = O.initial_state()
-    out = []
-    for ply in range(plies):
+    vec = E.start_state(start)
+    out = E.Played()
+    ply = -1
+    while plies is None or ply + 1 < plies:
+        ply += 1
         moves3, st = O.valid_moves(vec)
+        if plies is None and len(moves3) == 0:
+            return E.finish(out, ply, E.no_moves(st), False)
         assert len(moves3) > 0, "the game the device recorded goes on here"
         words = S.move_words(st, moves3)
         root_wtm = int(st[64])
         who = player_of(gid, root_wtm)
-        logits, _ = yield who, st
-        root, root_n = _Node(st, words, root_priors(logits, words, np_mt, eps, alpha)), 1
+        logits, root_value = yield who, st
+        root, root_n, n_pending = _Node(st, words, root_priors(logits, words, np_mt, eps, alpha)), 1, 0
         for _ in range(sims):
             node, n_par, path = root, root_n, []
             while True:
@@ -77,6 +87,7 @@ def game(seed, gid, sims, plies, sample_plies=0, c_puct=1.5, eps=0.0, alpha=0.3)
                     lw = S.move_words(lst, lm)
                     llog, v = yield who, lst  # the leaf row too is the root mover's net's
                     v = F(v)
+                    n_pending += 1
                     leaf_node.child[leaf_j] = _Node(lst, lw, leaf_priors(llog, lw))
             for d, (nd, j) in enumerate(path):
                 white_moved = (root_wtm != 0) ^ bool(d & 1)
@@ -94,7 +105,12 @@ def game(seed, gid, sims, plies, sample_plies=0, c_puct=1.5, eps=0.0, alpha=0.3)
             pick = visits.index(max(visits))
         out.append(dict(player=who, visits=visits, words=list(words), move=policy_index(words[pick]),
                         sampled=sampled))
+        out.extra.append(dict(board=bytes(st[:64]), root_value=F(root_value), pending=n_pending))
         vec = O.make_valid_move(vec, pick)
+        if plies is None:
+            end = E.after_move(vec, ply + 1, root_value, max_moves)
+            if end is not None:
+                return E.finish(out, ply + 1, end, True)
     return out
 
 

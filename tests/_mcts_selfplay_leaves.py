@@ -7,7 +7,8 @@ The game loop is that of tests/_mcts_selfplay_reuse.py (without carried trees)
 and tests/_mcts_arena.py: the two MT19937 streams of the game, the root's mixed
 priors, the move choice (random.choices over the visit counts, or their first
 maximum from ply `sample_plies` on), the player per ply, and the ply count told
-from outside, so no termination rule is restated. Each ply's search is the
+from outside -- or, with plies=None, the game played to its end by the rules of
+tests/_mcts_endings.py from any start position. Each ply's search is the
 sim-step loop of tests/_mcts_search.search: up to `leaves` descents per step
 under the in-flight counts V, the collision rule, backups in descent order.
 Every score is a numpy float32 operation in the kernel's order.
@@ -25,6 +26,7 @@ import numpy as np
 
 from oracle import oracle as O
 
+from tests import _mcts_endings as E
 from tests import _mcts_search as S
 from tests._mcts_arena import A, B, hash_eval_b, player_of  # noqa: F401  (also this module's names)
 from tests._mcts_search import leaf_priors, policy_index, root_priors
@@ -60,21 +62,29 @@ class _Node:
         self.cstate = [None] * n
 
 
-def game(seed, gid, sims, plies, leaves, arena=False, sample_plies=0, c_puct=1.5, eps=0.25, alpha=0.3):
+def game(seed, gid, sims, plies, leaves, arena=False, sample_plies=0, c_puct=1.5, eps=0.25, alpha=0.3, start=None,
+         max_moves=None):
     """`plies` plies of the game with global id `gid` whose two streams are seeded `seed` (the engine's seed +
     gid) at `leaves` descents per sim-step; arena: the player of a ply is the root's mover's (A is white iff gid
     is even), else always A. Returns one dict per ply: player, visits (root edge counts, list order), words (the
     root's move words), move (the record's index from * 64 + to), sampled (the move was drawn), accepted (per
     sim-step: the descents it accepted), leaf_pending (per sim-step: per accepted descent, the leaf went to the
-    network), root_value (the root row's value, which the engine's resignation rule reads)."""
+    network), root_value (the root row's value, which the engine's resignation rule reads); the list's `extra`
+    holds per ply the root's board (its 64 codes as bytes). start: the state vector the game starts from
+    (None: the initial position). plies None: the game is played to its end under max_moves by tests/_mcts_endings.py's rules and the list returned is an
+    E.Played with result (plies, outcome, reason, reward) and holds."""
     c = F(c_puct)
     ncap = sims + 2
     np_mt, py_mt = O.MT(seed, "numpy"), O.MT(seed, "python")
     sqt = [F(np.sqrt(np.float64(k))) for k in range(sims + 4)]
-    vec = O.initial_state()
-    out = []
-    for ply in range(plies):
+    vec = E.start_state(start)
+    out = E.Played()
+    ply = -1
+    while plies is None or ply + 1 < plies:
+        ply += 1
         moves3, st = O.valid_moves(vec)
+        if plies is None and len(moves3) == 0:
+            return E.finish(out, ply, E.no_moves(st), False)
         assert len(moves3) > 0, "the game the device recorded goes on here"
         words = S.move_words(st, moves3)
         root_wtm = int(st[64])
@@ -149,7 +159,12 @@ def game(seed, gid, sims, plies, leaves, arena=False, sample_plies=0, c_puct=1.5
             pick = visits.index(max(visits))
         out.append(dict(player=who, visits=visits, words=list(words), move=policy_index(words[pick]),
                         sampled=sampled, accepted=acc_steps, leaf_pending=pend_steps, root_value=F(root_value)))
+        out.extra.append(dict(board=bytes(st[:64])))
         vec = O.make_valid_move(vec, pick)
+        if plies is None:
+            end = E.after_move(vec, ply + 1, root_value, max_moves)
+            if end is not None:
+                return E.finish(out, ply + 1, end, True)
     return out
 
 
@@ -165,14 +180,16 @@ def play(seed, gid, sims, plies, leaves, evaluate_a=hash_eval, evaluate_b=hash_e
         return done.value
 
 
-def starts_of(plies, slots):
+def starts_of(plies, slots, holds=None):
     """The engine ply-step at which each game of a recycling run begins: the first `slots` games at 0, every
     later id in the slot that is free first (a game of n plies that ends on a committed move holds its slot for
-    n ply-steps; which of the slots freed in one ply-step takes which id does not matter here)."""
+    n ply-steps, one that ends with no legal move for n + 1: k_movegen finds that in a ply-step of its own --
+    holds: the ply-steps per game where they differ from plies, E.Played.holds; which of the slots freed in one
+    ply-step takes which id does not matter here)."""
     free = [0] * slots
     heapq.heapify(free)
     out = []
-    for n in plies:
+    for n in (plies if holds is None else holds):
         t = heapq.heappop(free)
         out.append(t)
         heapq.heappush(free, t + n)

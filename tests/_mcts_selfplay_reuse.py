@@ -10,13 +10,15 @@ Built from the oracle's rules (valid_moves, make_valid_move, is_draw,
 in_check), its two MT19937 streams (dirichlet, choices_index), its
 softmax_det_4096 / det_expf and the fp32 PUCT of tests/_mcts_search.py at one
 leaf, every score a numpy float32 operation in the kernel's order. The game is
-told how many plies to play (the device's own record count), so it restates no
-termination rule. Shared by tests/test_mcts_reuse_cpu.py and
+told how many plies to play (the device's own record count), or (plies=None)
+plays to the end by the rules of tests/_mcts_endings.py from any start
+position. Shared by tests/test_mcts_reuse_cpu.py and
 tests/test_mcts_reuse_gpu.py; not a test module itself."""
 import numpy as np
 
 from oracle import oracle as O
 
+from tests import _mcts_endings as E
 from tests import _mcts_search as S
 from tests._mcts_search import leaf_priors, policy_index, root_priors  # noqa: F401  (also this module's names)
 
@@ -67,7 +69,12 @@ def play(seed, sims, plies, reuse, evaluate=hash_eval, **kw):
     visits (root edge counts, list order), words (the root's move words), move (the record's index
     from * 64 + to), played_n (the played edge's count), carried (the root was a carried tree), kept (root
     visits carried in), rem (sim-steps run = sims - kept), pending (per sim-step: the leaf went to the
-    network), nodes (the tree's nodes at the choice)."""
+    network), nodes (the tree's nodes at the choice); the list's `extra` holds per ply board (the
+    root's 64 codes as bytes), root_value and child_kept (the played edge had a child: the tree the next ply of
+    the game carries). Keywords: start (the state vector
+    the game starts from; None: the initial position), max_moves; plies None: the game is played to its end
+    under max_moves by tests/_mcts_endings.py's rules and the list returned is an E.Played with result
+    (plies, outcome, reason, reward) and holds."""
     g = _play(seed, sims, plies, reuse, **kw)
     try:
         st = next(g)
@@ -100,19 +107,23 @@ def play_many(seeds, sims, plies, reuse, evaluate_many, **kw):
     return out
 
 
-def _play(seed, sims, plies, reuse, c_puct=1.5, eps=0.25, alpha=0.3):
+def _play(seed, sims, plies, reuse, c_puct=1.5, eps=0.25, alpha=0.3, start=None, max_moves=None):
     """The game as a generator: yields each position to evaluate, is sent (logits, value)."""
     c = F(c_puct)
     np_mt, py_mt = O.MT(seed, "numpy"), O.MT(seed, "python")
     sqt = [F(np.sqrt(np.float64(k))) for k in range(sims + 4)]
-    vec = O.initial_state()
+    vec = E.start_state(start)
     root, root_n, root_wtm = None, 1, 1
-    out = []
-    for _ in range(plies):
+    out = E.Played()
+    ply = -1
+    while plies is None or ply + 1 < plies:
+        ply += 1
         moves3, st = O.valid_moves(vec)
+        if plies is None and len(moves3) == 0:
+            return E.finish(out, ply, E.no_moves(st), False)
         assert len(moves3) > 0, "the game the device recorded goes on here"
         words = S.move_words(st, moves3)
-        logits, _ = yield st
+        logits, root_value = yield st
         priors = root_priors(logits, words, np_mt, eps, alpha)
         carried = root is not None
         if root is None:
@@ -165,7 +176,13 @@ def _play(seed, sims, plies, reuse, c_puct=1.5, eps=0.25, alpha=0.3):
         pick = py_mt.choices_index(np.array(visits, dtype=np.float64) / total)
         out.append(dict(visits=visits, words=list(words), move=policy_index(words[pick]), kept=kept, rem=rem,
                         carried=carried, pending=pending, nodes=_count_nodes(root), played_n=visits[pick]))
+        out.extra.append(dict(board=bytes(st[:64]), root_value=F(root_value),
+                              child_kept=bool(reuse) and root.child[pick] is not None))
         vec = O.make_valid_move(vec, pick)
+        if plies is None:
+            end = E.after_move(vec, ply + 1, root_value, max_moves)
+            if end is not None:
+                return E.finish(out, ply + 1, end, True)
         child = root.child[pick] if reuse else None
         if child is None:  # dropped: the next ply builds a fresh root
             root, root_n = None, 1

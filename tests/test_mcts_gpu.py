@@ -17,12 +17,13 @@ import pytest
 import torch
 
 from knightvision_amd import _lib
-from knightvision_amd.engine import EVAL_HASH, SelfPlayEngine, records_by_game, packed_from
+from knightvision_amd.engine import EVAL_HASH, SelfPlayEngine, records_by_game
 from knightvision_amd.weights import synthetic_state_dict
 
-pytestmark = pytest.mark.gpu
+from tests._mcts_network import CLASS_ROWS, count_ties
+from tests._mcts_network import hip_eval as _hip_eval
 
-CLASS_ROWS = 17  # smallest batch of the Winograd (> 16 boards) class
+pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("sims,max_moves,n", [(16, 60, 6), (64, 40, 4), (200, 24, 2)])
@@ -42,27 +43,6 @@ def test_mcts_hash_games_identical_to_oracle(sims, max_moves, n):
         assert reward == pytest.approx(r["reward"])
 
 
-def _hip_eval(sd, class_rows=CLASS_ROWS):
-    """Oracle evaluator: the HIP network's row for one board, computed in a
-    batch of class_rows copies (the engine's batch class: 17 = the > 16-board
-    Winograd class, 1 = the <= 16-board direct class of a one-slot engine)."""
-    from knightvision_amd.model import KVNet
-    net = KVNet(0, packed_from(sd))
-
-    def ev(planes):
-        planes = np.asarray(planes, dtype=np.float32).reshape(-1, 12, 64)
-        n = planes.shape[0]
-        codes = np.zeros((n, 64), dtype=np.int8)
-        b, c, sq = np.nonzero(planes)
-        codes[b, sq] = c + 1
-        rows = torch.from_numpy(np.repeat(codes, class_rows, axis=0)).cuda()
-        pol, val = net.forward_boards(rows)
-        torch.cuda.synchronize()
-        return pol.cpu().numpy()[::class_rows], val.cpu().numpy().reshape(-1)[::class_rows]
-
-    return ev, net
-
-
 def _compare_network_games(variant, slots, n_check, sims, max_moves, steps=-1):
     from oracle import oracle as O
     sd = synthetic_state_dict(42, variant)
@@ -75,21 +55,8 @@ def _compare_network_games(variant, slots, n_check, sims, max_moves, steps=-1):
         st = eng.stats()
     assert st["tree_overflows"] == 0
     ev, net = _hip_eval(sd)
-    ties = compared = 0
-    for g in range(n_check):
-        sel = recs["game_id"] == g
-        moves, vis = recs["move"][sel], visits[sel]
-        r = O.mcts_play_game(sims, O.MT(42 + g, "numpy"), O.MT(42 + g, "python"), ev,
-                             max_moves=max_moves if steps < 0 else len(moves), c_puct=1.5)
-        n = len(moves)
-        assert len(r["moves"]) >= n
-        for p in range(n):
-            compared += 1
-            if not (np.array_equal(vis[p], r["visits"][p]) and moves[p] == r["moves"][p]):
-                ties += 1
-                print(f"{variant} game {g} ply {p}: GPU visits {vis[p][vis[p] >= 0]} oracle "
-                      f"{r['visits'][p][r['visits'][p] >= 0]}")
-                break  # the games part here
+    compared, ties = count_ties(variant, recs, visits, range(n_check), lambda g, n: O.mcts_play_game(
+        sims, O.MT(42 + g, "numpy"), O.MT(42 + g, "python"), ev, max_moves=max_moves if steps < 0 else n, c_puct=1.5))
     net.close()
     print(f"MCTS network parity ({variant}, {slots} slots x {sims} sims): {compared} root visit vectors "
           f"compared, ties/divergences: {ties}")

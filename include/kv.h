@@ -205,7 +205,17 @@ typedef struct {
                              expansion that does not fit raises KV_EOVERFLOW (kv_stats.tree_overflows) */
     int keep_root_visits; /* 1: keep each MCTS move's root visit counts (pi) for kv_root_visits[_device];
                              2: as 1, and also each committed move's root move words for kv_root_moves[_device] */
-    int eval_cache;       /* Evaluation cache (DESIGN.md "Evaluation cache"): entries per network of an exact memo of the
+    int fast_sims;        /* Playout cap randomization (MCTS self-play, DESIGN.md "Playout cap randomization"). 0: off,
+                             every ply is searched to sims root visits (no kernel takes another path). Else
+                             1 <= fast_sims < sims: each ply is searched either full (sims visits) or fast (fast_sims
+                             visits, the root's Dirichlet noise drawn and weighted by 0); the kind is a pure function
+                             of cfg.seed + game id and the ply (full_q16). kv_record.pad bit 0 marks a fast ply.
+                             Needs sims >= 1 and arena 0; any other value: KV_EINVAL */
+    int full_q16;         /* fast_sims > 0: a ply is full when the top 16 bits of its 64-bit hash are below this,
+                             1..65536 (65536: every ply full). Must be 0 with fast_sims 0. (The two stand before
+                             eval_cache: the struct's last six fields stay eval_cache, leaves, arena, sample_plies,
+                             sim_groups, reuse_tree) */
+    int eval_cache;      /* Evaluation cache (DESIGN.md "Evaluation cache"): entries per network of an exact memo of the
                              leaf rows in HBM -- one table in self-play, two in an arena -- that kv_run's sim-step
                              probes before it builds the dense leaf batch and fills after the forward. 0: off (no launch,
                              argument or byte of the engine changes). Else a power of two in [64, 2^24], with leaves >= 2;
@@ -277,8 +287,8 @@ typedef struct {
     int64_t game_id;
     int32_t ply;
     uint16_t move;       /* encode_move index (ai/ai.py:51-57) */
-    uint16_t pad;
-    int8_t board[64];    /* position before the move (encode_board input) */
+    uint16_t pad;        /* bit 0: a fast ply of kv_config.fast_sims (not a policy target); else 0 */
+    int8_t board[64];   /* position before the move (encode_board input) */
 } kv_record;             /* 80 bytes */
 
 typedef struct {
@@ -314,7 +324,12 @@ typedef struct {
                                (the rest as 64x128 tiles in a second one; 100: one launch); 0 otherwise */
     char dom_kernel[96];    /* the name of the kernel those launches ran, as the library chose it (template
                                arguments included, e.g. "wino88i32_gemm_lagt_kernel<512,5>") */
-    int64_t arena_rows[2];   /* arena: the leaf-batch rows player A's / player B's net ran, padding included
+    int64_t plies_full;     /* committed plies searched to cfg.sims (== plies with kv_config.fast_sims 0) and */
+    int64_t plies_fast;     /* to cfg.fast_sims, counted at the move choice. reuse_tree 0: sims == plies_full x
+                               cfg.sims + plies_fast x cfg.fast_sims; reuse_tree 1: sims + sims_kept == the sum of
+                               the committed plies' root visit sums, each max(the ply's target, the visits carried
+                               in). (The two stand before arena_rows) */
+    int64_t arena_rows[2];  /* arena: the leaf-batch rows player A's / player B's net ran, padding included
                                (arena_rows[0] + arena_rows[1] == leaf_batch_rows); 0, 0 on a self-play engine */
     int64_t cache_probes;   /* kv_config.eval_cache: pending leaf rows probed (== leaf_rows_pending when kv_run returns), */
     int64_t cache_hits;     /* of those the rows an entry answered and the network did not run, */

@@ -21,7 +21,7 @@ class Config(C.Structure):
                 ("max_moves", C.c_int), ("batch", C.c_int), ("eps", C.c_double), ("alpha", C.c_double),
                 ("sims", C.c_int), ("c_puct", C.c_float), ("eval_mode", C.c_int), ("record_cap", C.c_int64),
                 ("recycle", C.c_int), ("precision", C.c_int), ("algo", C.c_int), ("tree_edge_cap", C.c_int),
-                ("keep_root_visits", C.c_int), ("eval_cache", C.c_int), ("leaves", C.c_int), ("arena", C.c_int), ("sample_plies", C.c_int),
+                ("keep_root_visits", C.c_int), ("fast_sims", C.c_int), ("full_q16", C.c_int), ("eval_cache", C.c_int), ("leaves", C.c_int), ("arena", C.c_int), ("sample_plies", C.c_int),
                 ("sim_groups", C.c_int), ("reuse_tree", C.c_int)]
 
 
@@ -41,6 +41,7 @@ class Stats(C.Structure):
                 ("res_conv_launches", C.c_int64), ("step_ms", C.c_double), ("dom_flop", C.c_double),
                 ("dom_algo", C.c_int64), ("tree_overflows", C.c_int64), ("nn_rows_lazy", C.c_int64),
                 ("dom_path", C.c_int64), ("dom_split", C.c_int64), ("dom_kernel", C.c_char * 96),
+                ("plies_full", C.c_int64), ("plies_fast", C.c_int64),
                 ("arena_rows", C.c_int64 * 2), ("cache_probes", C.c_int64), ("cache_hits", C.c_int64),
                 ("cache_stores", C.c_int64), ("sim_steps", C.c_int64), ("leaf_rows_pending", C.c_int64),
                 ("sims_kept", C.c_int64), ("roots_carried", C.c_int64), ("leaf_batch_rows", C.c_int64)]

@@ -66,6 +66,7 @@ struct Ctr {
     unsigned long long sims_kept;      // reuse_tree: root visits the committed plies' roots carried in
     unsigned long long roots_carried;  // reuse_tree: committed plies whose root was a carried tree
     int arena_n[2];  // arena: this ply's active slots whose mover plays on net A / net B (k_arena_split)
+    unsigned long long plies_fast;  // fast_sims: committed plies searched to the fast target (the rest are full)
 };
 
 struct DevCfg {
@@ -88,7 +89,25 @@ struct DevCfg {
     // state vectors, the game with global id g starts from starts[g % n_starts]
     const int8_t* starts;
     int n_starts;
+    int fast_sims;  // kv_config.fast_sims (0: off) and full_q16: a ply's kind and visit target (ply_target)
+    int full_q16;
 };
+
+// kv_config.fast_sims (DESIGN.md "Playout cap randomization"): the visit target of ply `ply` of game `game_id`, a
+// pure function of the value the game's two streams are seeded with and the ply -- sims on a full ply, fast_sims on
+// a fast one (*fast set). A splitmix64 finaliser over the two; no draw from either MT19937 stream.
+__device__ inline int ply_target(const DevCfg& cfg, long long game_id, int ply, bool* fast) {
+    unsigned long long x = (cfg.seed + (unsigned long long)game_id) * 0x9E3779B97F4A7C15ull +
+                           (unsigned long long)(ply + 1) * 0xD1B54A32D192ED03ull;
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    const bool full = (int)(x >> 48) < cfg.full_q16;
+    *fast = !full;
+    return full ? cfg.sims : cfg.fast_sims;
+}
 
 __device__ inline Pos slot_pos(const Slot& s, const int8_t* board) {
     Pos p;
@@ -149,7 +168,10 @@ struct Tree {  // per-slot SoA edge pools + node records, slot i at i*ecap / i*n
     int sims;
     uint16_t* e_V;  // position search with several leaves in flight (kv_search.hip): descents in flight per edge
     uint16_t* root_moves;  // optional [record_cap][MAXM]: the root's move words beside root_visits, 0xffff padded
-    int* rem;  // reuse_tree only (else NULL) [slot]: sim-steps the slot's next ply runs, sims - carried visits; 0: idle
+    // reuse_tree or fast_sims (else NULL) [slot]: sim-steps the slot's next ply runs, its target - carried visits; 0:
+    // idle, or a fast ply whose carried root already holds its target
+    int* rem;
+    int* tgt;  // fast_sims only (else NULL) [slot]: the visit target of the ply k_mcts_root built, sims or fast_sims
 };
 
 // ---- position search (kv_search.hip): per-tree state, per-(tree, j) descents of the running sim-step ----
@@ -327,20 +349,20 @@ __device__ void wave_softmax_4096_det(const float* lg, float* out, int lane) {
 // 256 threads of the slot's workgroup; gam is 4096 doubles of LDS.
 __device__ inline void mixed_legal_weights(const DevCfg& cfg, const float* lp, const uint16_t* ml, int n,
                                            double* gam, uint32_t* np_state, uint32_t* mt_ring, int* scratch,
-                                           double* vals, int tid) {
+                                           double* vals, int tid, double eps) {
     BlockMT w;
     bmt_load(w, np_state, mt_ring, tid);
     long long att;
     const double acc = block_dirichlet_gamma(w, cfg.alpha, 4096, gam, &att, scratch, tid);
     bmt_store(w, np_state, tid);
     const double invacc = 1 / acc;
-    const float keep = (float)(1.0 - cfg.eps);
+    const float keep = (float)(1.0 - eps);
     for (int j = tid; j < n; j += RNG_THREADS) {
         const int mv = ml[j];
         const int idx = (mv & 63) * 64 + ((mv >> 6) & 63);
         const float p32 = keep * lp[idx];
         const double noise = gam[idx] * invacc;
-        vals[j] = (double)p32 + cfg.eps * noise;
+        vals[j] = (double)p32 + eps * noise;
     }
     __syncthreads();
 }
@@ -377,7 +399,8 @@ __device__ inline int choose_weighted(const double* vals, double* cum, int n, ui
 // checks in order: isDraw (:180), resign (:185, `value` is the row the move
 // was chosen with), max_moves (:196). All lanes of the slot's wave.
 __device__ inline unsigned long long commit_move(const DevCfg& cfg, Slot& s, int i, int mv, int8_t* boards,
-                                                 kv_record* rec, int8_t* last_board, Ctr* ctr, int lane) {
+                                                 kv_record* rec, int8_t* last_board, Ctr* ctr, int lane,
+                                                 int flags = 0) {
     // lane = thread index of the slot's workgroup; lanes 0..63 (wave 0) carry
     // the 64 squares, every thread reaches the barriers
     int8_t* board = boards + (size_t)i * 64;
@@ -392,7 +415,7 @@ __device__ inline unsigned long long commit_move(const DevCfg& cfg, Slot& s, int
             rec[ridx].game_id = s.game_id;
             rec[ridx].ply = s.ply;
             rec[ridx].move = (uint16_t)((mv & 63) * 64 + ((mv >> 6) & 63));
-            rec[ridx].pad = 0;
+            rec[ridx].pad = (uint16_t)flags;  // bit 0: a fast ply (kv_config.fast_sims)
         }
     } else if (lane == 0) {
         atomicOr(&ctr->error, 2);
@@ -440,6 +463,8 @@ int mcts_backup_select(const DevCfg& cfg, const Tree& t, const Slot* slots, cons
                        int count, bool reuse = false, const int* list = nullptr);
 // reuse_tree: after k_finish, every slot's tree carried (re-rooted on the played edge's child) or dropped
 int mcts_carry(const DevCfg& cfg, const Tree& t, const Slot* slots, Ctr* ctr, hipStream_t st);
+// fast_sims without reuse_tree: after k_finish, every slot's rem = its next ply's visit target
+int mcts_targets(const DevCfg& cfg, const Tree& t, const Slot* slots, hipStream_t st);
 int mcts_choose(const DevCfg& cfg, const Tree& t, Slot* slots, int8_t* boards, uint32_t* py_mt, kv_record* rec,
                 int8_t* last_board, Ctr* ctr, hipStream_t st);
 // negate: the arena's player B under KV_EVAL_HASH (the same rows with the value negated)

@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     __syncthreads();
     const int n = s.nmoves;
     const uint16_t* ml = moves + (size_t)i * MAXM;
-    mixed_legal_weights(cfg, lp, ml, n, gam, np_mt + (size_t)i * MT_WORDS, mt3, scratch, vals, lane);
+    mixed_legal_weights(cfg, lp, ml, n, gam, np_mt + (size_t)i * MT_WORDS, mt3, scratch, vals, lane, cfg.eps);
     // random.choices (:162-167): the total, then random() drawn by the whole
     // workgroup (a twist of the CPython state, every 312 plies of a game, runs
     // block-parallel in LDS -- one slot's serial twist would stretch the launch)
@@ -390,10 +390,11 @@ __global__ __launch_bounds__(1024) void k_compact(DevCfg cfg, const Slot* slots,
 // = the slot's row or -1. The network is batch-invariant bit for bit inside a
 // class, so every active slot's leaf row equals its row in the full batch and
 // the searches are unchanged (tests/test_mcts_gpu.py). With kv_config.reuse_tree (node != NULL) the batch is
-// that of the slots still searching inside a ply: active and live, the root holding fewer than sims visits.
+// that of the slots still searching inside a ply: active and live, the root holding fewer than sims visits
+// (kv_config.fast_sims, tgt != NULL: fewer than the ply's own target tgt[i]).
 __global__ __launch_bounds__(1024) void k_compact_active(DevCfg cfg, const Slot* slots, int rows, int* slot_of,
                                                          int* row_of, Ctr* ctr, const NodeRec* node, int ncap,
-                                                         int sims) {
+                                                         int sims, const int* tgt) {
     __shared__ int wsum[16];
     __shared__ int base;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -402,7 +403,7 @@ __global__ __launch_bounds__(1024) void k_compact_active(DevCfg cfg, const Slot*
     for (int c0 = 0; c0 < cfg.slots; c0 += 1024) {
         const int i = c0 + tid;
         const bool act = i < cfg.slots && slots[i].status == ST_ACTIVE &&
-                         (node == nullptr || node[(size_t)i * ncap].N - 1 < sims);
+                         (node == nullptr || node[(size_t)i * ncap].N - 1 < (tgt ? tgt[i] : sims));
         const unsigned long long bal = __ballot(act);
         if (lane == 0) wsum[w] = __popcll(bal);
         __syncthreads();
@@ -512,7 +513,7 @@ __global__ __launch_bounds__(1024) void k_arena_split(DevCfg cfg, const Slot* sl
 __global__ __launch_bounds__(1024) void k_leaves_compact(DevCfg cfg, const Slot* slots, const SearchSlot* ss,
                                                          const int* lcnt, int L, int sims, int arena, int cap,
                                                          int pad_to, int* list_a, int* list_b, int* row_of,
-                                                         LeafCtr* lc, Ctr* ctr, const int* hit) {
+                                                         LeafCtr* lc, Ctr* ctr, const int* hit, const int* tgt) {
     __shared__ int wsum[2][16];
     __shared__ int base[2];
     __shared__ int s_step, s_rem;
@@ -524,7 +525,7 @@ __global__ __launch_bounds__(1024) void k_leaves_compact(DevCfg cfg, const Slot*
     for (int i = tid; i < cfg.slots; i += 1024) {
         const SearchSlot q = ss[i];
         step += q.accepted > 0;
-        rem += q.accepted > 0 && q.done + q.accepted < sims;
+        rem += q.accepted > 0 && q.done + q.accepted < (tgt ? tgt[i] : sims);  // (fast_sims: the ply's own target)
     }
     if (step) atomicAdd(&s_step, step);
     if (rem) atomicAdd(&s_rem, rem);
@@ -864,6 +865,18 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
                "kv_create: arena with reuse_tree: a tree grown on one net's rows is not the other player's");
     KV_REQUIRE(cfg->arena == 0 || cfg->eval_mode != KV_EVAL_LAZY, KV_EINVAL,
                "kv_create: arena with eval_mode KV_EVAL_LAZY (lazy: reference move selection only)");
+    KV_REQUIRE(cfg->fast_sims >= 0 && (cfg->fast_sims == 0 || cfg->sims == 0 || cfg->fast_sims < cfg->sims), KV_EINVAL,
+               "kv_create: fast_sims %d out of range: 0 (off) or 1 <= fast_sims < sims (%d)", cfg->fast_sims, cfg->sims);
+    KV_REQUIRE(cfg->fast_sims == 0 || cfg->sims >= 1, KV_EINVAL,
+               "kv_create: fast_sims %d with sims 0: the fast search is a PUCT search and needs sims >= 1",
+               cfg->fast_sims);
+    KV_REQUIRE(cfg->fast_sims != 0 || cfg->full_q16 == 0, KV_EINVAL,
+               "kv_create: full_q16 %d with fast_sims 0: it is ignored with the feature off and must be 0",
+               cfg->full_q16);
+    KV_REQUIRE(cfg->fast_sims == 0 || (cfg->full_q16 >= 1 && cfg->full_q16 <= 65536), KV_EINVAL,
+               "kv_create: full_q16 %d out of range [1, 65536] (65536: every ply full)", cfg->full_q16);
+    KV_REQUIRE(cfg->fast_sims == 0 || cfg->arena == 0, KV_EINVAL,
+               "kv_create: fast_sims %d with arena 1: a match measures strength at the full search", cfg->fast_sims);
     KV_REQUIRE(cfg->sample_plies >= -1, KV_EINVAL,
                "kv_create: sample_plies %d must be 0 (every ply drawn), k > 0 (first maximum from ply k on) or -1 "
                "(first maximum on every ply)", cfg->sample_plies);
@@ -897,6 +910,8 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     d.sample_plies = cfg->sample_plies;
     d.starts = nullptr;
     d.n_starts = 0;
+    d.fast_sims = cfg->fast_sims;
+    d.full_q16 = cfg->full_q16;
     e->leaves = std::max(cfg->leaves, 1);
     e->big = e->leaves > 1 ? (long long)cfg->slots * e->leaves > 16 : cfg->slots > 16;
     // several leaves in the > 16-row class: a root batch of fewer than 17 slots is padded to 17 rows (empty boards)
@@ -969,7 +984,11 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
             ALLOC(e->mc_logits, S * kv::MAXM * sizeof(float));
             ALLOC(e->mc_values, S * sizeof(float));
         }
-        if (cfg->reuse_tree) ALLOC(t.rem, S * sizeof(int));
+        if (cfg->reuse_tree || cfg->fast_sims > 0) ALLOC(t.rem, S * sizeof(int));
+        if (cfg->fast_sims > 0) {
+            ALLOC(t.tgt, S * sizeof(int));
+            (void)hipMemset(t.tgt, 0, S * sizeof(int));
+        }
         if (e->leaves > 1) {
             kv::SearchWs& w = e->lw;
             const size_t rows = S * (size_t)e->leaves, RR = std::max<size_t>(rows, 17);
@@ -1089,8 +1108,10 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
     hipLaunchKernelGGL(kv::k_init, dim3((cfg->slots + 63) / 64), dim3(64), 0, e->st, d, e->slots, e->boards,
                        e->np_mt, e->py_mt, e->ctr);
     KV_HIP(hipGetLastError());
-    // reuse_tree: no slot holds a tree yet -- rem = sims for the slots k_init started, 0 for the idle ones
-    if (e->tree.rem && (rc = kv::mcts_carry(d, e->tree, e->slots, e->ctr, e->st))) {
+    // reuse_tree: no slot holds a tree yet -- rem = sims (fast_sims: ply 0's target, with or without reuse_tree) for
+    // the slots k_init started, 0 for the idle ones
+    if (e->tree.rem && (rc = cfg->reuse_tree ? kv::mcts_carry(d, e->tree, e->slots, e->ctr, e->st)
+                                             : kv::mcts_targets(d, e->tree, e->slots, e->st))) {
         kv_destroy(e);
         return rc;
     }
@@ -1277,6 +1298,8 @@ static int eng_group_sims(kv_engine* e, int k0, int k1, int steps, bool reuse) {
 // the active and live slots, rebuilt at every step whose live count is lower than at the last rebuild by at
 // least KV_REUSE_COMPACT_STEP. A slot that k_movegen finished this ply only makes the host's counts upper
 // bounds (padding rows); more live slots on the device than the batch holds raise error flag 16.
+// kv_config.fast_sims takes this path with or without reuse_tree: rem is then each slot's own target less its carried
+// visits (k_mcts_carry / k_mcts_targets), 0 for a fast ply whose carried root already holds its target.
 static int eng_reuse_sims(kv_engine* e, int act) {
     const kv::Tree& t = e->tree;
     const int S = e->cfg.slots, sims = e->dc.sims;
@@ -1290,20 +1313,21 @@ static int eng_reuse_sims(kv_engine* e, int act) {
         steps = std::max(steps, r);
         counted += r > 0;
     }
-    KV_REQUIRE(counted == act, KV_EHIP, "kv_run: %d active slots, %d with sim-steps to run (reuse_tree)", act,
-               counted);
+    // (fast_sims with reuse_tree: a fast ply whose carried root already holds its target runs no step)
+    KV_REQUIRE(t.tgt && e->cfg.reuse_tree ? counted <= act : counted == act, KV_EHIP,
+               "kv_run: %d active slots, %d with sim-steps to run (reuse_tree / fast_sims)", act, counted);
     e->sim_steps += steps;
     if ((rc = kv::mcts_root(e->dc, t, e->slots, e->moves, e->logits, e->values, e->probs, e->np_mt, e->ctr, e->st)))
         return rc;
     if ((rc = kv::mcts_select(e->dc, t, e->slots, e->boards, e->nn_boards, e->ctr, e->st, 0, S, true))) return rc;
-    int live = act;      // slots with rem > k
+    int live = counted;  // slots with rem > k
     int compacted = -1;  // the live count at the last compaction of this ply (-1: none yet)
     int R = 0;
     // two slot groups: the leading steps at which every slot is live (the full-slot batch) run as groups; from
     // the first compact batch on the ply runs as one group
     int kg = 0;
-    if (e->groups == 2 && act == S) {
-        int lv = act;
+    if (e->groups == 2 && counted == S) {
+        int lv = counted;
         for (; kg < steps; ++kg) {
             if (kg > 0) lv -= hist[kg];
             if (e->mc_slot_of != nullptr && lv < S) break;  // step kg runs the compact batch
@@ -1318,7 +1342,8 @@ static int eng_reuse_sims(kv_engine* e, int act) {
             if (compacted < 0 || compacted - live >= KV_REUSE_COMPACT_STEP) {
                 R = S > 16 ? std::max(live, 17) : live;
                 hipLaunchKernelGGL(kv::k_compact_active, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, R,
-                                   e->mc_slot_of, e->mc_row_of, e->ctr, (const kv::NodeRec*)t.node, t.ncap, sims);
+                                   e->mc_slot_of, e->mc_row_of, e->ctr, (const kv::NodeRec*)t.node, t.ncap, sims,
+                                   (const int*)t.tgt);
                 KV_HIP(hipGetLastError());
                 compacted = live;
             }
@@ -1543,7 +1568,7 @@ static int eng_leaves_ply(kv_engine* e, int act) {
         hipLaunchKernelGGL(kv::k_leaves_compact, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, w.ss, w.lcnt, L, sims,
                            e->cfg.arena, std::max(rows, 17), pad_to, e->lf_list[0],
                            e->lf_list[1] ? e->lf_list[1] : e->lf_list[0], e->lf_row_of, e->lf_ctr, e->ctr,
-                           cache ? e->ec_hit : nullptr);
+                           cache ? e->ec_hit : nullptr, (const int*)t.tgt);
         KV_HIP(hipGetLastError());
         KV_HIP(hipMemcpyAsync(e->lf_ctr_host, e->lf_ctr, sizeof(kv::LeafCtr), hipMemcpyDeviceToHost, e->st));
         KV_HIP(hipStreamSynchronize(e->st));
@@ -1651,7 +1676,8 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
                 e->sim_steps += e->dc.sims;
                 if (comp) {
                     hipLaunchKernelGGL(kv::k_compact_active, dim3(1), dim3(1024), 0, e->st, e->dc, e->slots, R,
-                                       e->mc_slot_of, e->mc_row_of, e->ctr, (const kv::NodeRec*)nullptr, 0, 0);
+                                       e->mc_slot_of, e->mc_row_of, e->ctr, (const kv::NodeRec*)nullptr, 0, 0,
+                                       (const int*)nullptr);
                     KV_HIP(hipGetLastError());
                 }
                 if ((rc = kv::mcts_root(e->dc, t, e->slots, e->moves, e->logits, e->values, e->probs, e->np_mt, e->ctr, e->st)))
@@ -1689,7 +1715,9 @@ int kv_run(kv_engine* e, int64_t max_steps, int64_t stop_after_games) {
         hipLaunchKernelGGL(kv::k_finish, dim3(S), dim3(128), 0, e->st, e->dc, e->slots, e->boards,
                            e->moves, e->np_mt, e->py_mt, e->games, e->ctr);
         KV_HIP(hipGetLastError());
-        if (e->tree.rem && (rc = kv::mcts_carry(e->dc, e->tree, e->slots, e->ctr, e->st))) return rc;
+        if (e->tree.rem && (rc = e->cfg.reuse_tree ? kv::mcts_carry(e->dc, e->tree, e->slots, e->ctr, e->st)
+                                                   : kv::mcts_targets(e->dc, e->tree, e->slots, e->st)))
+            return rc;
         ++done;
         ++e->steps;
         if (done % check_every == 0 || (max_steps >= 0 && done >= max_steps)) {
@@ -1830,7 +1858,10 @@ int kv_search(kv_engine* e, const int8_t* states, int n, const kv_search_params*
     int rc = search_reserve(e, n, L);
     if (rc) return rc;
     const kv::SearchWs& w = e->sw;
-    const kv::Tree& t = e->tree;
+    kv::Tree ts = e->tree;  // (kv_config.fast_sims is self-play's: a search has one target, its own sims)
+    ts.tgt = nullptr;
+    if (!e->cfg.reuse_tree) ts.rem = nullptr;
+    const kv::Tree& t = ts;
     hipStream_t st = e->st;
     // a search that overflowed a shrunk pool leaves the engine usable: the flag is this search's own
     KV_HIP(hipMemsetAsync(&e->ctr->error, 0, sizeof(int), st));
@@ -1943,7 +1974,10 @@ int kv_search_continue(kv_engine* e, int n, const kv_search_params* p, kv_search
     int rc = search_reserve(e, n, L);
     if (rc) return rc;
     const kv::SearchWs& w = e->sw;
-    const kv::Tree& t = e->tree;
+    kv::Tree ts = e->tree;  // (kv_config.fast_sims is self-play's: a search has one target, its own sims)
+    ts.tgt = nullptr;
+    if (!e->cfg.reuse_tree) ts.rem = nullptr;
+    const kv::Tree& t = ts;
     hipStream_t st = e->st;
     // what the host knows of the roots: the dropped trees take a root row, the longest top-up bounds the steps
     bool any_fresh = false;
@@ -2103,6 +2137,8 @@ int kv_stats_get(kv_engine* e, kv_stats* out) {
     out->sims_kept = (int64_t)e->ctr_host->sims_kept;
     out->roots_carried = (int64_t)e->ctr_host->roots_carried;
     out->leaf_batch_rows = e->mc_rows + e->full_rows;
+    out->plies_fast = (int64_t)e->ctr_host->plies_fast;
+    out->plies_full = out->plies - out->plies_fast;
     out->arena_rows[0] = e->arena_rows[0];
     out->arena_rows[1] = e->arena_rows[1];
     kv::CacheCtr cc = {0, 0, 0};
@@ -2208,7 +2244,7 @@ void kv_destroy(kv_engine* e) {
                     e->mc_logits, e->mc_values,
                     t.e_V, e->sw.ss, e->sw.lf, e->sw.paths, e->sw.lboards, e->sw.lmoves, e->sw.lcnt, e->sw.llogits,
                     e->sw.lvalues, e->sw.remaining, e->sw.res, e->s_states, e->s_rboards, e->s_rlogits,
-                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves, t.rem,
+                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves, t.rem, t.tgt,
                     e->ar_row_of, e->ar_list[0], e->ar_list[1], e->ar_boards[0], e->ar_boards[1], e->ar_moves[0],
                     e->ar_moves[1], e->ar_cnt[0], e->ar_cnt[1], e->ar_llogits[0], e->ar_llogits[1], e->ar_values[0],
                     e->ar_values[1], e->ar_rlogits[0], e->ar_rlogits[1],

@@ -31,6 +31,10 @@
 // With kv_config.reuse_tree the subtree under the move just played is carried into the next ply
 // (k_mcts_carry, DESIGN.md "Carried subtrees in self-play"): the root takes the fresh root's mixed priors, N,
 // W and the children below it stay, and a slot searches only while its root holds fewer than sims visits.
+// With kv_config.fast_sims (DESIGN.md "Playout cap randomization") every ply has a visit target of its own, sims or
+// fast_sims (ply_target, kv_engine.h): k_mcts_root_pcr writes it into Tree::tgt and mixes a fast ply's noise in with
+// eps = 0, the REUSE kernels search a slot while its root holds fewer visits than that, and rem is written against
+// the next ply's target (k_mcts_carry, or k_mcts_targets without reuse_tree).
 // Tree: structure-of-arrays edge pools per slot in HBM (move u16, P f32, N u16,
 // W f32, child u16 per edge: 14 B; a node's edges start on a 16-edge boundary)
 // and one 16-byte record per node (first edge, edge count; N for the root only:
@@ -45,9 +49,13 @@
 
 namespace kv {
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_mcts_root(DevCfg cfg, Tree t, Slot* slots, const uint16_t* moves,
-                                                   const float* logits, const float* values, float* probs,
-                                                   uint32_t* np_mt, Ctr* ctr) {
+// one slot's root, by the 256 threads of its workgroup. PCR (kv_config.fast_sims, Tree::tgt != NULL): the ply's
+// visit target is written and a fast ply mixes its noise in with eps = 0; the false instance is the kernel without
+// the feature
+template <bool PCR>
+__device__ __forceinline__ void mcts_root_slot(const DevCfg& cfg, const Tree& t, Slot* slots, const uint16_t* moves,
+                                               const float* logits, const float* values, float* probs,
+                                               uint32_t* np_mt, Ctr* ctr) {
     __shared__ uint32_t mt3[MT_RW];
     __shared__ double gam[4096];
     __shared__ double vals[MAXM];
@@ -60,7 +68,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     __syncthreads();
     const int n = s.nmoves;
     const uint16_t* ml = moves + (size_t)i * MAXM;
-    mixed_legal_weights(cfg, lp, ml, n, gam, np_mt + (size_t)i * MT_WORDS, mt3, scratch, vals, lane);
+    // kv_config.fast_sims: the ply's visit target; a fast ply's noise is drawn as ever and weighted by 0
+    double eps = cfg.eps;
+    if (PCR) {
+        bool fast;
+        const int target = ply_target(cfg, s.game_id, s.ply, &fast);
+        if (fast) eps = 0.0;
+        if (lane == 0) t.tgt[i] = target;
+    }
+    mixed_legal_weights(cfg, lp, ml, n, gam, np_mt + (size_t)i * MT_WORDS, mt3, scratch, vals, lane, eps);
     __shared__ double s_total;
     if (lane == 0) {
         double total = 0.0;
@@ -126,8 +142,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     }
 }
 
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_mcts_root(DevCfg cfg, Tree t, Slot* slots, const uint16_t* moves,
+                                                   const float* logits, const float* values, float* probs,
+                                                   uint32_t* np_mt, Ctr* ctr) {
+    mcts_root_slot<false>(cfg, t, slots, moves, logits, values, probs, np_mt, ctr);
+}
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_mcts_root_pcr(
+    DevCfg cfg, Tree t, Slot* slots, const uint16_t* moves, const float* logits, const float* values, float* probs,
+    uint32_t* np_mt, Ctr* ctr) {
+    mcts_root_slot<true>(cfg, t, slots, moves, logits, values, probs, np_mt, ctr);
+}
+
 // one slot's select, by the 64 threads of its workgroup. REUSE (kv_config.reuse_tree): a slot whose root
-// already holds sims visits (carried ones counting) is not live: no descent, no leaf
+// already holds sims visits (carried ones counting; with kv_config.fast_sims the ply's own target, Tree::tgt) is not
+// live: no descent, no leaf
 template <bool REUSE>
 __device__ inline void mcts_select_slot(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards,
                                         int8_t* nn_boards, Ctr* ctr, int i) {
@@ -135,7 +164,7 @@ __device__ inline void mcts_select_slot(const DevCfg& cfg, const Tree& t, const 
     __shared__ int s_meta[8];  // wtm wkr wkc bkr bkc flags ep
     const int lane = threadIdx.x;
     const Slot s = slots[i];
-    if (s.status != ST_ACTIVE || (REUSE && t.node[(size_t)i * t.ncap].N - 1 >= t.sims)) {
+    if (s.status != ST_ACTIVE || (REUSE && t.node[(size_t)i * t.ncap].N - 1 >= (t.tgt ? t.tgt[i] : t.sims))) {
         if (lane == 0) t.leaf_cnt[i] = 0;  // no logits for this row of the batch
         return;
     }
@@ -222,7 +251,7 @@ __device__ inline void mcts_backup_slot(const DevCfg& cfg, const Tree& t, const 
     const int lane = threadIdx.x;
     const Slot s = slots[i];
     if (s.status != ST_ACTIVE) return;
-    if (REUSE && t.node[(size_t)i * t.ncap].N - 1 >= t.sims) return;
+    if (REUSE && t.node[(size_t)i * t.ncap].N - 1 >= (t.tgt ? t.tgt[i] : t.sims)) return;
     MctsSlot m = t.ms[i];
     const size_t eb = (size_t)i * t.ecap, nb = (size_t)i * t.ncap;
     float v = m.leaf_value;
@@ -355,7 +384,14 @@ __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* sl
         // reuse_tree: the ply's new backups; the visits its root carried in are counted beside them, at the
         // choice like sims, so that sims + sims_kept == plies x cfg.sims whenever kv_run returns
         const int kept = t.rem != nullptr ? m.pad[4] : 0;
-        atomicAdd(&ctr->sims, (unsigned long long)(cfg.sims - kept));
+        if (t.tgt != nullptr) {
+            // fast_sims: the ply's own target; a carried root that already held it ran no step
+            const int target = t.tgt[i];
+            atomicAdd(&ctr->sims, (unsigned long long)(target > kept ? target - kept : 0));
+            if (target != cfg.sims) atomicAdd(&ctr->plies_fast, 1ull);
+        } else {
+            atomicAdd(&ctr->sims, (unsigned long long)(cfg.sims - kept));
+        }
         atomicAdd(&ctr->nn_rows, (unsigned long long)m.pad[1]);
         if (t.rem != nullptr) {
             t.ms[i].pad[3] = s_pick;  // the played root edge, for k_mcts_carry
@@ -367,7 +403,9 @@ __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* sl
     }
     s.last_value = m.root_value;  // resign test on the root's network value (:185)
     s.n_evals += m.pad[0];
-    const unsigned long long ridx = commit_move(cfg, s, i, t.e_move[eb + s_pick], boards, rec, last_board, ctr, lane);
+    const int fast_ply = t.tgt != nullptr && t.tgt[i] != cfg.sims ? 1 : 0;  // kv_record.pad bit 0
+    const unsigned long long ridx =
+        commit_move(cfg, s, i, t.e_move[eb + s_pick], boards, rec, last_board, ctr, lane, fast_ply);
     if (t.root_visits && (long long)ridx < cfg.record_cap) {
         uint16_t* rv = t.root_visits + (size_t)ridx * MAXM;
         for (int j = lane; j < MAXM; j += 64) rv[j] = j < n ? t.e_N[eb + j] : (uint16_t)0xffff;
@@ -419,7 +457,23 @@ __global__ __launch_bounds__(64) void k_mcts_carry(DevCfg cfg, Tree t, const Slo
         m.root_wtm = s.wtm;  // the side to move after the committed move: the old root's, flipped
     }
     t.ms[i] = m;
-    t.rem[i] = s.status != ST_ACTIVE ? 0 : carried ? t.sims - (played_n - 1) : t.sims;
+    int target = t.sims;  // fast_sims: the next ply's own (k_mcts_root writes the same value into Tree::tgt)
+    if (t.tgt != nullptr) {
+        bool fast;
+        target = ply_target(cfg, s.game_id, s.ply, &fast);
+    }
+    const int kept = carried ? played_n - 1 : 0;
+    t.rem[i] = s.status != ST_ACTIVE ? 0 : target > kept ? target - kept : 0;
+}
+
+// kv_config.fast_sims without reuse_tree, once per ply after k_finish in k_mcts_carry's place: rem[i] = the next
+// ply's visit target (every root is fresh), 0 for a slot that is not active
+__global__ __launch_bounds__(64) void k_mcts_targets(DevCfg cfg, Tree t, const Slot* slots) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= cfg.slots) return;
+    const Slot s = slots[i];
+    bool fast;
+    t.rem[i] = s.status != ST_ACTIVE ? 0 : ply_target(cfg, s.game_id, s.ply, &fast);
 }
 
 // Test evaluator (KV_EVAL_HASH): all logits 0 (uniform priors, exact in
@@ -454,8 +508,12 @@ int hash_legal(const Tree& t, int rows, hipStream_t st) {
 
 int mcts_root(const DevCfg& cfg, const Tree& t, Slot* slots, const uint16_t* moves, const float* logits,
               const float* values, float* probs, uint32_t* np_mt, Ctr* ctr, hipStream_t st) {
-    hipLaunchKernelGGL(k_mcts_root, dim3(cfg.slots), dim3(256), 0, st, cfg, t, slots, moves, logits, values, probs,
-                       np_mt, ctr);
+    if (t.tgt != nullptr)
+        hipLaunchKernelGGL(k_mcts_root_pcr, dim3(cfg.slots), dim3(256), 0, st, cfg, t, slots, moves, logits, values,
+                           probs, np_mt, ctr);
+    else
+        hipLaunchKernelGGL(k_mcts_root, dim3(cfg.slots), dim3(256), 0, st, cfg, t, slots, moves, logits, values,
+                           probs, np_mt, ctr);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
@@ -507,6 +565,12 @@ int mcts_choose(const DevCfg& cfg, const Tree& t, Slot* slots, int8_t* boards, u
 
 int mcts_carry(const DevCfg& cfg, const Tree& t, const Slot* slots, Ctr* ctr, hipStream_t st) {
     hipLaunchKernelGGL(k_mcts_carry, dim3(cfg.slots), dim3(64), 0, st, cfg, t, slots, ctr);
+    KV_HIP(hipGetLastError());
+    return KV_OK;
+}
+
+int mcts_targets(const DevCfg& cfg, const Tree& t, const Slot* slots, hipStream_t st) {
+    hipLaunchKernelGGL(k_mcts_targets, dim3((cfg.slots + 63) / 64), dim3(64), 0, st, cfg, t, slots);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }

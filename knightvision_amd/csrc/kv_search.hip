@@ -96,9 +96,11 @@ __global__ __launch_bounds__(64) void k_search_load(Tree t, SearchWs w, Slot* sl
 // one tree's descents of a sim-step, by the 64 threads of its workgroup. SP: the tree is a self-play slot's
 // (kv_config.leaves > 1, k_leaves_* below): it is searched while the slot is active and its root holds fewer than
 // sims backups, and ss.done is written for the step's compaction (sims for a slot that takes no descent)
+// (kv_config.fast_sims: fewer than the ply's own target, Tree::tgt)
 template <bool HASV, bool SP = false>
 __device__ inline void search_select_tree(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards,
                                           Ctr* ctr, int sims, int L, int i) {
+    if (SP && t.tgt != nullptr) sims = t.tgt[i];
     __shared__ int8_t root_bd[64];
     __shared__ int8_t bd[64];
     __shared__ int s_meta[8];                // wtm wkr wkc bkr bkc flags ep

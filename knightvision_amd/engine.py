@@ -49,7 +49,7 @@ class SelfPlayEngine:
                  batch=16, eps=0.25, alpha=0.3, sims=0, c_puct=1.5, eval_mode=EVAL_FAITHFUL, record_cap=None,
                  recycle=True, device=0, game_id_base=0, game_id_stride=1, precision="fp32",
                  algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False, reuse_tree=False,
-                 sim_groups=0, opponent=None, sample_plies=0, leaves=0, eval_cache=0):
+                 sim_groups=0, opponent=None, sample_plies=0, leaves=0, eval_cache=0, fast_sims=0, full_prob=0.25):
         """opponent (MCTS, sims >= 1): a second weight set makes the engine an arena (kv_config.arena): `weights`
         is player A, `opponent` player B, A plays white in the games with an even global id, and every ply is
         searched on the net of the side to move; games()["outcome"] stays white-perspective (arena.summarize
@@ -68,7 +68,12 @@ class SelfPlayEngine:
         a power of two in [64, 2^24], 0 off: a leaf whose board and move list were evaluated before takes the stored
         logits and value and leaves the step's network batch. Play is byte for byte the play without it; stats()
         reports cache_probes / cache_hits / cache_stores, and nn_rows - cache_hits rows ran on the network.
-        load_weights / load_opponent empty the table of the net they replace."""
+        load_weights / load_opponent empty the table of the net they replace.
+        fast_sims (MCTS self-play; kv_config.fast_sims): 0 off; 1 <= fast_sims < sims turns on playout cap
+        randomization -- each ply is searched to `sims` root visits with probability full_prob and to fast_sims
+        otherwise (a pure function of seed, game id and ply; full_q16 = round(full_prob * 65536) clipped to
+        [1, 65536]). A fast ply's record has pad bit 0 set (fast_mask): it gives a value target and no policy
+        target. stats() reports plies_full / plies_fast. Not with an opponent."""
         L = _lib.lib()
         keep = 2 if keep_root_moves else (1 if keep_root_visits else 0)  # the move words imply the visits
         if record_cap is None:
@@ -78,6 +83,7 @@ class SelfPlayEngine:
             per_game = int(max_moves) if max_moves else 1024
             # (the side buffers are 640 B per record each: 2^22 records with the visits, 2^21 with the moves too)
             record_cap = max(1 << 16, min(1 << {0: 27, 1: 22, 2: 21}[keep], int(n_games) * per_game))
+        full_q16 = min(max(int(round(float(full_prob) * 65536)), 1), 65536) if int(fast_sims) else 0
         cfg = _lib.Config(device=device, slots=slots, n_games=n_games, game_id_base=game_id_base,
                           game_id_stride=game_id_stride, seed=seed, seed_mode=seed_mode,
                           max_moves=max_moves if max_moves else 0, batch=batch, eps=eps, alpha=alpha, sims=sims,
@@ -85,7 +91,8 @@ class SelfPlayEngine:
                           precision=PRECISIONS[precision], algo=ALGOS[algo],
                           tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep, reuse_tree=int(reuse_tree),
                           sim_groups=int(sim_groups), arena=0 if opponent is None else 1,
-                          sample_plies=int(sample_plies), leaves=int(leaves), eval_cache=int(eval_cache))
+                          sample_plies=int(sample_plies), leaves=int(leaves), eval_cache=int(eval_cache),
+                          fast_sims=int(fast_sims), full_q16=full_q16)
         h = C.c_void_p()
         _lib.check(L.kv_create(C.byref(cfg), C.byref(h)), "kv_create")
         self.h = h
@@ -357,6 +364,11 @@ class PositionSearch:
             self.close()
         except Exception:
             pass
+
+
+def fast_mask(recs: np.ndarray) -> np.ndarray:
+    """bool[n]: the records of fast plies (kv_record.pad bit 0, kv_config.fast_sims): value targets only."""
+    return (np.asarray(recs["pad"]) & 1).astype(bool)
 
 
 def records_by_game(recs: np.ndarray, games: np.ndarray):

@@ -30,6 +30,13 @@ dataset tuple carries them as sparse PolicyTargets (policy_targets.py) and
 the update step scores them with the fused HIP loss (train_ops.policy_loss).
 The default, "move", is the reference's loss.
 
+fast_sims > 0 (no reference counterpart; MCTS self-play only) turns on playout
+cap randomization (kv_config.fast_sims, DESIGN.md "Playout cap randomization"):
+a ply is searched to `sims` visits with probability full_prob, else to
+fast_sims. Every record gives a value target; in "visits" mode only the full
+plies give a policy target (PolicyTargets.w is 0 on the fast ones). "move"
+mode trains on every record as before.
+
 arena_games > 0 (no reference counterpart; the reference evaluates against
 Stockfish here, learn.py:204-206): after an iteration's update the new weights
 play a match against the weights the iteration started from (arena.py,
@@ -50,7 +57,7 @@ import torch
 
 from . import train as T
 from .distributed import gather_rows
-from .engine import SelfPlayEngine, packed_from
+from .engine import SelfPlayEngine, fast_mask, packed_from
 from .policy_targets import PolicyTargets
 from .self_play import ALPHA, BATCH_SIZE as SELFPLAY_BATCH, EPSILON, SEED
 
@@ -73,7 +80,8 @@ def _dist():
 
 
 def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_moves=None, slots=256,
-                   precision="fp32", policy_targets=False, reuse_tree=False, leaves=0, eval_cache=0):
+                   precision="fp32", policy_targets=False, reuse_tree=False, leaves=0, eval_cache=0, fast_sims=0,
+                   full_prob=0.25):
     """This rank's share of one iteration's games, played by the HIP engine with
     the model's current weights. Returns (records, games) numpy arrays; with
     policy_targets (MCTS runs) also the root visit counts and root move words of
@@ -82,7 +90,9 @@ def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_m
     the subtree under each move played into the next ply (kv_config.reuse_tree); every root still holds sims
     visits, so the visit targets are built as without it. leaves > 1 (sims > 0): that many descents in flight
     per game and sim-step (kv_config.leaves); eval_cache (leaves >= 2): entries of the engine's exact leaf-row cache
-    (kv_config.eval_cache; 0: off), which changes no record."""
+    (kv_config.eval_cache; 0: off), which changes no record. fast_sims > 0 (0 < fast_sims < sims): playout cap
+    randomization (kv_config.fast_sims) -- a ply is searched to sims visits with probability full_prob and to
+    fast_sims otherwise; the records of fast plies carry pad bit 0 (engine.fast_mask)."""
     dist, rank, world = _dist()
     dev = torch.device(device)
     ids = list(range(rank, n_games, world))
@@ -97,7 +107,7 @@ def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_m
                         game_id_base=base, game_id_stride=world, device=dev.index or 0,
                         precision=precision, eval_mode=batched_eval_mode() if sims == 0 else 0,
                         keep_root_moves=bool(policy_targets), reuse_tree=bool(reuse_tree), leaves=int(leaves),
-                        eval_cache=int(eval_cache)) as eng:
+                        eval_cache=int(eval_cache), fast_sims=int(fast_sims), full_prob=float(full_prob)) as eng:
         eng.run()
         selfplay_shard.last_calibration = eng.calibration()  # the conv paths these weights ran on
         selfplay_shard.last_stats = eng.stats()
@@ -158,29 +168,41 @@ def decisive_filter(codes, moves, rewards, targets=None):
     return (codes, moves, rewards) if targets is None else (codes, moves, rewards, targets)
 
 
-def _gather_targets(recs, games, pi, dev) -> PolicyTargets:
+def _gather_targets(recs, games, pi, dev, weighted=False) -> PolicyTargets:
     """This iteration's visit targets of every rank, in gather_rows' rank order (the order the samples'
     tensors take): each row's legal-move prefix (distributed.pack_pi) of the visit counts and of the move
-    words crosses ranks, and the CSR is built from that compact form directly."""
+    words crosses ranks, and the CSR is built from that compact form directly. weighted (fast_sims > 0, the
+    same on every rank): the targets carry per-sample weights, 0 on the records of fast plies and 1 on the
+    others, which cross ranks beside the rows' lengths."""
     if recs is not None and len(recs):
         if pi is None:
             raise ValueError("extend_dataset: policy_targets needs the records' (visits, moves) of selfplay_shard")
         keep = np.isin(recs["game_id"], games["game_id"])  # records_to_tensors' rows: the finished games'
-        local = PolicyTargets.from_engine(pi[0][keep], pi[1][keep], dev)
+        local = PolicyTargets.from_engine(pi[0][keep], pi[1][keep], dev,
+                                          weights=1.0 - fast_mask(recs[keep]) if weighted else None)
     else:
         local = PolicyTargets.empty(dev)
     counts = local.lengths().to(torch.int16)
+    if weighted:  # (length, weight) pairs: one exchange for both
+        pairs = torch.stack([counts, local.weights().to(torch.int16)], 1).contiguous()
+        pairs = gather_rows(pairs.view(torch.uint8).reshape(-1, 4), dst=None).to(dev).contiguous()
+        pairs = pairs.view(torch.int16).reshape(-1, 2)
 
     def all_ranks(t):  # int16 travels as byte pairs (gloo has no int16 collectives)
         return gather_rows(t.view(torch.uint8).reshape(-1, 2), dst=None).to(dev).contiguous().view(torch.int16).reshape(-1)
 
-    counts, idx, cnt = all_ranks(counts), all_ranks(local.idx), all_ranks(local.cnt)
+    w = None
+    if weighted:
+        counts, w = pairs[:, 0].contiguous(), pairs[:, 1].to(torch.float32)
+    else:
+        counts = all_ranks(counts)
+    idx, cnt = all_ranks(local.idx), all_ranks(local.cnt)
     off = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=dev)
     off[1:] = torch.cumsum(counts.to(torch.int64) & 0xffff, 0)
-    return PolicyTargets(off, idx, cnt)
+    return PolicyTargets(off, idx, cnt, w)
 
 
-def extend_dataset(data, recs, games, dev, pi=None, policy_targets=False):
+def extend_dataset(data, recs, games, dev, pi=None, policy_targets=False, weighted=False):
     """dataset.extend(generate_self_play_data(...)) for one iteration
     (learn.py:194-199): the ranks' new records are all-gathered (the one
     end-of-iteration exchange) and filtered as one dataset (the reference's
@@ -191,7 +213,8 @@ def extend_dataset(data, recs, games, dev, pi=None, policy_targets=False):
     selfplay_shard, row for row with `recs` (None on a rank without games); the
     visit targets are gathered and filtered with the samples and the dataset
     tuple carries them as a fourth element, samples that came without a search
-    holding their one-hot row."""
+    holding their one-hot row. weighted (fast_sims > 0): the targets carry the
+    per-sample policy weights (_gather_targets)."""
     if recs is not None and len(recs):
         local = T.records_to_tensors(recs, games, dev)
     else:
@@ -201,7 +224,7 @@ def extend_dataset(data, recs, games, dev, pi=None, policy_targets=False):
         union = decisive_filter(*(gather_rows(x, dst=None).to(dev) for x in local))
         return union if data is None else tuple(torch.cat([a, b]) for a, b in zip(data, union))
     union = tuple(gather_rows(x, dst=None).to(dev) for x in local)
-    union = decisive_filter(*union, _gather_targets(recs, games, pi, dev))
+    union = decisive_filter(*union, _gather_targets(recs, games, pi, dev, weighted))
     if data is None:
         return union
     old = data[3] if len(data) > 3 else PolicyTargets.one_hot(data[1])
@@ -294,7 +317,8 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
                        seed: int = 0, games_path: str | None = None, max_samples: int = 10000, log=print,
                        policy_target: str = "move", reuse_tree: bool = False, arena_games: int = 0,
                        arena_sims: int | None = None, leaves: int = 0, arena_leaves: int | None = None,
-                       eval_cache: int = 0, arena_eval_cache: int | None = None):
+                       eval_cache: int = 0, arena_eval_cache: int | None = None, fast_sims: int = 0,
+                       full_prob: float = 0.25):
     """Run the loop (learn.py reinforcement_loop :152-209); returns per-iteration statistics.
     `model` is a knightvision_amd.model.ChessNet (same parameters as ai/model.py) on `device`.
     `games_path`: the reference's JSONL dataset (ChessPGNDataset, :162) the self-play records extend --
@@ -314,7 +338,13 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
     `leaves` (sims > 0): descents in flight per game and sim-step in self-play (kv_config.leaves; 0 or 1: one);
     `arena_leaves`: the same for the matches (None: `leaves`).
     `eval_cache` (leaves >= 2): entries of the self-play engine's exact leaf-row cache (kv_config.eval_cache; 0: off);
-    `arena_eval_cache`: the same per net for the matches (None: `eval_cache`). Neither changes a game."""
+    `arena_eval_cache`: the same per net for the matches (None: `eval_cache`). Neither changes a game.
+    `fast_sims` > 0 (0 < fast_sims < sims; no reference counterpart): playout cap randomization in self-play
+    (kv_config.fast_sims) -- each ply is searched to `sims` visits with probability `full_prob`, else to
+    `fast_sims`. The statistics gain plies_full / plies_fast. With policy_target="visits" only the full plies'
+    visit distributions train the policy (PolicyTargets.w, train.batch_loss); every record trains the value
+    head. policy_target="move" trains on every record, fast plies included, as before. The matches
+    (`arena_games`) always search every ply to `arena_sims`."""
     if policy_target not in ("move", "visits"):
         raise ValueError(f"reinforcement_loop: policy_target {policy_target!r}: 'move' or 'visits'")
     if arena_games > 0 and (arena_sims if arena_sims is not None else sims) <= 0:
@@ -366,11 +396,13 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
         if visits:
             recs, games, *pi = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves,
                                               slots=slots, policy_targets=True, reuse_tree=reuse_tree,
-                                              leaves=leaves, eval_cache=eval_cache)
+                                              leaves=leaves, eval_cache=eval_cache, fast_sims=fast_sims,
+                                              full_prob=full_prob)
             pi = None if recs is None else tuple(pi)
         else:
             recs, games = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves, slots=slots,
-                                         reuse_tree=reuse_tree, leaves=leaves, eval_cache=eval_cache)
+                                         reuse_tree=reuse_tree, leaves=leaves, eval_cache=eval_cache,
+                                         fast_sims=fast_sims, full_prob=full_prob)
         st["selfplay_s"] = time.perf_counter() - t0
         cal = getattr(selfplay_shard, "last_calibration", None)
         if cal is not None:  # fp32 AUTO: the self-play network's conv path for this iteration's weights
@@ -381,9 +413,10 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
         es = getattr(selfplay_shard, "last_stats", None)
         if es is not None:  # this rank's engine: plies and MCTS simulations (the throughput a path flip moves)
             st.update(plies=int(es["plies"]), sims=int(es["sims"]), sims_kept=int(es["sims_kept"]),
-                      leaf_batch_rows=int(es["leaf_batch_rows"]), sim_steps=int(es["sim_steps"]))
+                      leaf_batch_rows=int(es["leaf_batch_rows"]), sim_steps=int(es["sim_steps"]),
+                      plies_full=int(es["plies_full"]), plies_fast=int(es["plies_fast"]))
         model.train()
-        data = extend_dataset(data, recs, games, dev, pi=pi, policy_targets=True) if visits \
+        data = extend_dataset(data, recs, games, dev, pi=pi, policy_targets=True, weighted=fast_sims > 0) if visits \
             else extend_dataset(data, recs, games, dev)
         st.update(records=int(data[0].shape[0]) if data is not None else 0,
                   games=int(len(games)) if games is not None else 0)

@@ -19,6 +19,13 @@ SelfPlayEngine.root_moves()) is (w & 63) * 64 + ((w >> 6) & 63), the index
 kv_net_forward_boards_legal documents. A sample without a search (a PGN / JSONL
 sample, a record of a sims = 0 run) gets the one-entry row (move, 1), whose
 soft cross-entropy is the hard one.
+
+Optional per-sample weights `w` (float32 [N]; None: none, every consumer then
+takes the code path it always took): 1 for a sample whose row is a policy
+target, 0 for one whose row is not -- a fast ply of playout cap randomization
+(kv_config.fast_sims), searched too shallowly to train the policy on. They are
+filtered, indexed and concatenated with the rows (a part without weights counts
+as all ones), and train.batch_loss weighs the policy term by them.
 """
 from __future__ import annotations
 
@@ -52,10 +59,14 @@ def _padded_rows(x, device) -> torch.Tensor:
 
 
 class PolicyTargets:
-    def __init__(self, off: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor):
+    def __init__(self, off: torch.Tensor, idx: torch.Tensor, cnt: torch.Tensor, w: torch.Tensor | None = None):
         assert off.dtype == torch.int64 and idx.dtype == torch.int16 and cnt.dtype == torch.int16
         assert off.dim() == 1 and off.numel() >= 1 and idx.shape == cnt.shape and idx.dim() == 1
         self.off, self.idx, self.cnt = off.contiguous(), idx.contiguous(), cnt.contiguous()
+        if w is not None:
+            assert w.dim() == 1 and w.numel() == off.numel() - 1
+            w = w.to(device=off.device, dtype=torch.float32).contiguous()
+        self.w = w
 
     def __len__(self) -> int:
         return int(self.off.numel()) - 1
@@ -69,7 +80,12 @@ class PolicyTargets:
         return int(self.idx.numel())
 
     def to(self, device) -> "PolicyTargets":
-        return PolicyTargets(self.off.to(device), self.idx.to(device), self.cnt.to(device))
+        return PolicyTargets(self.off.to(device), self.idx.to(device), self.cnt.to(device),
+                             None if self.w is None else self.w.to(device))
+
+    def weights(self) -> torch.Tensor:
+        """The per-sample weights float32 [N]; all ones when the targets carry none."""
+        return self.w if self.w is not None else torch.ones(len(self), dtype=torch.float32, device=self.device)
 
     def lengths(self) -> torch.Tensor:
         return self.off[1:] - self.off[:-1]
@@ -91,9 +107,10 @@ class PolicyTargets:
         return PolicyTargets(off, move_word_index(words).to(torch.int16), visits.to(torch.int16))
 
     @staticmethod
-    def from_engine(visits, moves, device="cpu") -> "PolicyTargets":
+    def from_engine(visits, moves, device="cpu", weights=None) -> "PolicyTargets":
         """visits / moves uint16 [n, MAXM] (SelfPlayEngine.root_visits() / root_moves(), row for row; the
-        visits' -1 padding reads as 0xffff): each row's legal-move prefix, zero counts kept."""
+        visits' -1 padding reads as 0xffff): each row's legal-move prefix, zero counts kept. weights: optional
+        [n] per-sample weights (1 - engine.fast_mask(records) with kv_config.fast_sims)."""
         v, m = _padded_rows(visits, device), _padded_rows(moves, device)
         if v.shape != m.shape:
             raise ValueError(f"PolicyTargets.from_engine: visits {tuple(v.shape)} and moves {tuple(m.shape)} differ")
@@ -101,7 +118,14 @@ class PolicyTargets:
         cm, pm = pack_pi(m)
         if not torch.equal(cv, cm):
             raise ValueError("PolicyTargets.from_engine: a row's visits and move words differ in length")
-        return PolicyTargets.from_packed(cv, pv, pm)
+        out = PolicyTargets.from_packed(cv, pv, pm)
+        if weights is not None:
+            wt = torch.as_tensor(np.asarray(weights, dtype=np.float32) if not isinstance(weights, torch.Tensor)
+                                 else weights).reshape(-1)
+            if wt.numel() != len(out):
+                raise ValueError(f"PolicyTargets.from_engine: {wt.numel()} weights for {len(out)} rows")
+            out = PolicyTargets(out.off, out.idx, out.cnt, wt)
+        return out
 
     @staticmethod
     def one_hot(move_index: torch.Tensor) -> "PolicyTargets":
@@ -119,8 +143,11 @@ class PolicyTargets:
         for p in parts:
             offs.append(p.off[1:].to(dev) + base)
             base += p.nnz
+        w = None
+        if any(p.w is not None for p in parts):  # a part without weights: every row a policy target
+            w = torch.cat([p.weights().to(dev) for p in parts])
         return PolicyTargets(torch.cat(offs), torch.cat([p.idx.to(dev) for p in parts]),
-                             torch.cat([p.cnt.to(dev) for p in parts]))
+                             torch.cat([p.cnt.to(dev) for p in parts]), w)
 
     # ---- row operations
     def select(self, rows: torch.Tensor) -> "PolicyTargets":
@@ -134,7 +161,7 @@ class PolicyTargets:
         off[1:] = torch.cumsum(ln, 0)
         # entry e of the new row r comes from self.off[rows[r]] + (e - off[r])
         src = torch.repeat_interleave(self.off[rows] - off[:-1], ln) + torch.arange(int(off[-1]), device=self.device)
-        return PolicyTargets(off, self.idx[src], self.cnt[src])
+        return PolicyTargets(off, self.idx[src], self.cnt[src], None if self.w is None else self.w[rows])
 
     __getitem__ = select
 

@@ -120,7 +120,9 @@ def batch_loss(model, b: Batch, entropy_coef: float = ENTROPY_COEF, amp: bool = 
     (loss, loss_policy, loss_value, entropy, policy_logits). A batch that carries
     PolicyTargets (Batch.targets / rows) replaces the policy term by the mean soft
     cross-entropy against the visit distributions, the entropy coming from the same
-    fused op (train_ops.policy_loss); no reference counterpart."""
+    fused op (train_ops.policy_loss); no reference counterpart. Targets that carry per-sample weights
+    (PolicyTargets.w: 0 on the fast plies of kv_config.fast_sims) weigh the policy term,
+    (ce * w).sum() / max(w.sum(), 1); the entropy and value terms run over all rows."""
     dev_type = b.boards.device.type
     if bucket is None:
         bucket = ROW_BUCKET if dev_type == "cuda" else 0
@@ -132,7 +134,7 @@ def batch_loss(model, b: Batch, entropy_coef: float = ENTROPY_COEF, amp: bool = 
     if b.targets is not None:
         from .train_ops import policy_loss
         ce, ent = policy_loss(pol, b.targets, b.rows)
-        loss_policy, entropy = ce.mean(), ent.mean()
+        loss_policy, entropy = _policy_term(ce, b.targets, b.rows), ent.mean()
         loss_value = F.mse_loss(val.squeeze().float(), b.outcomes)
         loss = loss_policy + loss_value - entropy_coef * entropy
         return loss, loss_policy, loss_value, entropy, pol
@@ -142,6 +144,15 @@ def batch_loss(model, b: Batch, entropy_coef: float = ENTROPY_COEF, amp: bool = 
     entropy = -(F.softmax(pol.float(), dim=1) * logp).sum(dim=1).mean()
     loss = loss_policy + loss_value - entropy_coef * entropy
     return loss, loss_policy, loss_value, entropy, pol
+
+
+def _policy_term(ce: torch.Tensor, targets, rows: torch.Tensor) -> torch.Tensor:
+    """The batch's policy loss from its per-row soft cross-entropies: their mean, or with per-sample weights
+    (PolicyTargets.w) the weighted mean over the rows that are policy targets."""
+    if targets.w is None:
+        return ce.mean()
+    w = targets.w[rows.to(targets.w.device)].to(ce.device)
+    return (ce * w).sum() / w.sum().clamp(min=1.0)
 
 
 def _finite_on_all_ranks(loss: torch.Tensor, force: bool = False) -> bool:
@@ -210,7 +221,7 @@ def evaluate(model, data) -> float:
         pol, val = model(b.boards)
         if b.targets is not None:  # the target the update trains on
             from .train_ops import policy_loss
-            lp = policy_loss(pol, b.targets, b.rows)[0].mean()
+            lp = _policy_term(policy_loss(pol, b.targets, b.rows)[0], b.targets, b.rows)
         else:
             lp = F.cross_entropy(pol.float(), b.moves)
         lv = F.mse_loss(val.squeeze().float(), b.outcomes)

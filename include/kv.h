@@ -477,6 +477,9 @@ int kv_dev_valid_moves(int device, const int8_t* states, int n, uint16_t* moves_
  * attacked[i] is set when an opponent pseudo-move of state i ends on (r, c);
  * inCheck (:388-394) is the bit of the mover's stored king location. */
 int kv_dev_attacks(int device, const int8_t* states, int n, uint64_t* attacked);
+/* kv_dev_attacks' attack set computed on the host CPU: the same source (targets(), csrc/kv_movegen.h)
+ * compiled for the host, so tests can pin it against the reference's recorded sets without a GPU. */
+int kv_host_attacks(const int8_t* states, int n, uint64_t* attacked);
 /* makeMove (chessEngine.py:127-197) of move index[i] of each state's list. */
 int kv_dev_make_move(int device, int8_t* states, const int* index, int n);
 /* Where the engine's games start (tests only: self-play and the arena have no opening book). states: n >= 1

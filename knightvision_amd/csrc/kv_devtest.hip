@@ -75,16 +75,19 @@ __global__ __launch_bounds__(64) void k_dev_make(int8_t* states, const int* inde
 
 // squareUnderAttack's set for the side to move (chessEngine.py:400-415): end
 // squares of every opponent pseudo-move, one bit per square
-__global__ void k_dev_attacks(const int8_t* states, int n, unsigned long long* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int8_t* v = states + (size_t)i * 80;
+__host__ __device__ inline unsigned long long attacks_of(const int8_t* v) {
     Pos p;
     pos_from_board(p, v, v[64], v[65], v[66], v[67], v[68],
                    (v[69] ? F_WKM : 0) | (v[70] ? F_BKM : 0) | (v[71] ? F_WRK : 0) | (v[72] ? F_WRQ : 0) |
                        (v[73] ? F_BRK : 0) | (v[74] ? F_BRQ : 0),
                    v[75] < 0 ? -1 : v[75] * 8 + v[76]);
-    out[i] = targets(p, p.wtm ? 1 : 0);
+    return targets(p, p.wtm ? 1 : 0);
+}
+
+__global__ void k_dev_attacks(const int8_t* states, int n, unsigned long long* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = attacks_of(states + (size_t)i * 80);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) void k_dev_dirichlet(const unsigned long long* seeds, double alpha, int k,
@@ -160,6 +163,12 @@ int kv_dev_attacks(int device, const int8_t* states, int n, uint64_t* attacked) 
     KV_HIP(hipGetLastError());
     KV_HIP(hipDeviceSynchronize());
     KV_HIP(hipMemcpy(attacked, o.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return KV_OK;
+}
+
+int kv_host_attacks(const int8_t* states, int n, uint64_t* attacked) {
+    KV_REQUIRE(n > 0 && states && attacked, KV_EINVAL, "kv_host_attacks: bad arguments");
+    for (int i = 0; i < n; ++i) attacked[i] = kv::attacks_of(states + (size_t)i * 80);
     return KV_OK;
 }
 

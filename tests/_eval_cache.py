@@ -1,6 +1,7 @@
 """Plain-Python restatement of the evaluation cache (kv_config.eval_cache, DESIGN.md "Evaluation cache";
 knightvision_amd/csrc/kv_cache.hip): the hash, the direct-mapped table, the rule of one sim-step, and a driver that
-plays tests/_mcts_selfplay_leaves' games with the step batches behind a cache per player.
+plays tests/_mcts_selfplay_leaves' games with the step batches behind a cache per player -- also with more games
+than slots, where a recycled slot's new game finds the entries the finished games stored.
 
 Semantics, as include/kv.h states them:
 
@@ -97,19 +98,24 @@ class Table:
         self.slot = [None] * self.entries
 
 
-def run_step(table, keys, run_misses):
+def run_step(table, keys, run_misses, log=None):
     """One sim-step on one table. keys: the step's pending rows in list order; run_misses(list of their indices)
-    -> one payload per missed row (the network). -> (payload per row, the missed indices)."""
+    -> one payload per missed row (the network). -> (payload per row, the missed indices). log: a dict that
+    takes the rule's own account of the step -- stored: the indices whose rows were stored, lost: the misses that
+    lost their entry to an earlier miss of the list."""
     found = [table.probe(k) for k in keys]
     miss = [i for i, p in enumerate(found) if p is None]
     out = list(found)
-    claimed = {}
+    claimed, lost = {}, []
     for i, p in zip(miss, run_misses(miss) if miss else []):
         out[i] = p
         if table.entries and len(keys[i][1]) <= CACHE_MAXM:
-            claimed.setdefault(table.index(keys[i]), i)  # the earliest miss of the list on an entry
+            if claimed.setdefault(table.index(keys[i]), i) != i:  # the earliest miss of the list on an entry
+                lost.append(i)
     for i in sorted(claimed.values()):
         table.store(keys[i], out[i])
+    if log is not None:
+        log.update(stored=sorted(claimed.values()), lost=lost)
     return out, miss
 
 
@@ -134,6 +140,10 @@ class CachedEval:
         self.dup_steps = 0       # steps that held two equal rows
         self.emptied = 0         # non-empty lists the hits emptied
         self.cut_below_class = 0  # lists of >= 17 rows cut to 1 .. 16 misses
+        self.row_games = None    # set by play_many_cached before a leaves() call: the game of each row
+        self.stored_by = {}      # key -> the game whose row was stored under it last
+        self.hits_from = []      # per hit of a tagged list: (the probing game, the game that stored the entry)
+        self.contests = 0        # misses that lost an entry to an earlier miss of their step
 
     def roots(self, states):
         return self.ev(states)
@@ -149,8 +159,15 @@ class CachedEval:
             return [(tuple(np.asarray(lg, dtype=F)[[S.policy_index(w) for w in kw[i][1]]].view(np.uint32).tolist()),
                      int(np.asarray(v, dtype=F).view(np.uint32))) for i, (lg, v) in zip(miss, rows)]
 
-        out, miss = run_step(self.table, keys, run)
+        log = {}
+        out, miss = run_step(self.table, keys, run, log)
         self.steps.append((len(states), miss))
+        self.contests += len(log["lost"])
+        tags, self.row_games = self.row_games, None
+        if tags is not None:
+            assert len(tags) == len(keys)
+            self.hits_from += [(tags[i], self.stored_by[keys[i]]) for i in range(len(keys)) if i not in miss]
+            self.stored_by.update((keys[i], tags[i]) for i in log["stored"])
         m = len(miss)
         self.batch_rows += self.pad_to if 0 < m < self.pad_to else m
         self.dup_steps += len(set(keys)) < len(keys)
@@ -164,16 +181,45 @@ class CachedEval:
         return rows
 
 
-def play_many_cached(seeds, gids, sims, plies, leaves, cache_a, cache_b=None, per_game=None, **kw):
-    """tests/_mcts_selfplay_leaves.play_many for games that all start at ply-step 0 (no recycling, so list order
-    is game order), the root batches through cache_x.roots and every step's batch through cache_x.leaves.
-    per_game: one dict of further SL.game keywords per game (its start position).
+def seating(holds, slots):
+    """Where and when each game of a recycling run sits: the first `slots` games take slots 0 .. slots - 1 at
+    ply-step 0, every later id the slot that is free first (tests/_mcts_selfplay_leaves.starts_of; holds: the
+    ply-steps each game keeps its slot). -> (starts, slot_of, ties): ties counts the later games that found more
+    than one slot freed in the same ply-step -- on the device those slots draw their ids in no fixed order
+    (k_finish's atomic counter), so only a run without ties has one seating."""
+    free = [(0, i) for i in range(slots)]
+    starts, slot_of, ties = [], [], 0
+    for g, n in enumerate(holds):
+        t, i = min(free)
+        if g >= slots and sum(1 for ft, _ in free if ft == t) > 1:
+            ties += 1
+        free.remove((t, i))
+        starts.append(t)
+        slot_of.append(i)
+        free.append((t + n, i))
+    return starts, slot_of, ties
+
+
+def play_many_cached(seeds, gids, sims, plies, leaves, cache_a, cache_b=None, per_game=None, starts=None,
+                     slot_of=None, **kw):
+    """tests/_mcts_selfplay_leaves.play_many, the root batches through cache_x.roots and every step's batch
+    through cache_x.leaves. per_game: one dict of further SL.game keywords per game (its start position).
+    starts / slot_of (seating): the ply-step each game begins at and the engine slot it sits in -- more games than
+    slots; a step's list is in slot order, which is game order only while no slot has been recycled. Without them
+    every game starts at ply-step 0 in the slot of its index.
     -> (per-game outputs, dict(steps, pending: [A's, B's], batches: per sim-step the (A's, B's) pending rows))."""
     per_game = per_game or [{}] * len(seeds)
     gens = [SL.game(s, g, sims, n, leaves, **kw, **pg) for s, g, n, pg in zip(seeds, gids, plies, per_game)]
     ev = (cache_a, cache_b or cache_a)
+    starts = list(starts) if starts is not None else [0] * len(gens)
+    slot_of = list(slot_of) if slot_of is not None else list(range(len(gens)))
     out, req = [None] * len(gens), {}
     info = dict(steps=0, pending=[0, 0], batches=[])
+
+    def by_slot(ks):
+        ks = sorted(ks, key=lambda k: slot_of[k])
+        assert len({slot_of[k] for k in ks}) == len(ks), "two games in one slot"
+        return ks
 
     def advance(k, val=None):
         try:
@@ -182,17 +228,19 @@ def play_many_cached(seeds, gids, sims, plies, leaves, cache_a, cache_b=None, pe
             out[k] = done.value
             req.pop(k, None)
 
-    for k in range(len(gens)):
-        advance(k)
-    while req:
+    eply = 0
+    while req or any(s >= eply for s in starts):
+        for k, s in enumerate(starts):
+            if s == eply:
+                advance(k)
         assert all(kind == "root" for kind, _, _ in req.values())
         for x in (SL.A, SL.B):
-            ks = sorted(k for k in req if req[k][1] == x)
+            ks = by_slot(k for k in req if req[k][1] == x)
             if ks:
                 for k, row in zip(ks, ev[x].roots([req[k][2] for k in ks])):
                     advance(k, row)
         while True:
-            stepping = sorted(k for k in req if req[k][0] == "step")
+            stepping = by_slot(k for k in req if req[k][0] == "step")
             if not stepping:
                 break
             info["steps"] += 1
@@ -201,6 +249,7 @@ def play_many_cached(seeds, gids, sims, plies, leaves, cache_a, cache_b=None, pe
                 ks = [k for k in stepping if req[k][1] == x]
                 states = [st for k in ks for st in req[k][2]]
                 counts[x] = len(states)
+                ev[x].row_games = [k for k in ks for _ in req[k][2]]
                 rows = iter(ev[x].leaves(states))
                 for k in ks:
                     got[k] = [next(rows) for _ in req[k][2]]
@@ -209,6 +258,7 @@ def play_many_cached(seeds, gids, sims, plies, leaves, cache_a, cache_b=None, pe
             info["batches"].append(tuple(counts))
             for k in stepping:
                 advance(k, got[k])
+        eply += 1
     return out, info
 
 

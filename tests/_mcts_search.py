@@ -216,10 +216,11 @@ def leaf_rows_of(evaluate, pending):
     return [(leaf_priors(lg, w), F(v)) for (lg, v), (_, w) in zip(rows, pending)]
 
 
-def search(state, sims, leaves=1, c_puct=1.5, ncap=None, evaluate=None, eps=0.0, alpha=0.3, seed=0):
+def search(state, sims, leaves=1, c_puct=1.5, ncap=None, evaluate=None, eps=0.0, alpha=0.3, seed=0, depths=False):
     """-> dict(status, visits, q, prior, moves, best, pv, steps, nn_rows, root_value, sims: the root's visits,
     accepted: the descents each sim-step accepted). evaluate(list of states after getValidMoves) -> [(logits[4096] float32, value
-    float32)], None: the hash evaluator; seed: the position's own stream (the call's seed + its index)."""
+    float32)], None: the hash evaluator; seed: the position's own stream (the call's seed + its index).
+    depths: the dict also holds `depths`, per sim-step the path lengths of its accepted descents."""
     c = F(c_puct)
     ncap = sims + 2 if ncap is None else ncap
     state = np.array(state, dtype=np.int8)
@@ -236,7 +237,7 @@ def search(state, sims, leaves=1, c_puct=1.5, ncap=None, evaluate=None, eps=0.0,
     priors, root_value = fresh_root_row(evaluate, st, words, eps, alpha, seed)
     root = _Node(st, words, priors)
     root_wtm = int(st[64])
-    root_n, done, steps, leaf_rows, per_step = 1, 0, 0, 0, []
+    root_n, done, steps, leaf_rows, per_step, path_lens = 1, 0, 0, 0, [], []
     sqt = [F(np.sqrt(np.float64(k))) for k in range(sims + 4)]
     while done < sims:
         r = min(leaves, sims - done)
@@ -300,6 +301,7 @@ def search(state, sims, leaves=1, c_puct=1.5, ncap=None, evaluate=None, eps=0.0,
         done += len(accepted)
         steps += 1
         per_step.append(len(accepted))
+        path_lens.append([len(path) for path, _, _ in accepted])
     visits = list(root.N)
     q = [root.W[j] / F(root.N[j]) if root.N[j] > 0 else F(0.0) for j in range(n)]
     pv, node = [], root
@@ -312,9 +314,10 @@ def search(state, sims, leaves=1, c_puct=1.5, ncap=None, evaluate=None, eps=0.0,
         if node.child[j] is None:
             break
         node = node.child[j]
+    more = dict(depths=path_lens) if depths else {}
     return dict(status=SEARCHED, visits=visits, q=q, prior=list(root.P), moves=list(root.words),
                 best=visits.index(max(visits)), pv=pv, steps=steps, nn_rows=1 + leaf_rows, accepted=per_step,
-                root_value=root_value, sims=done)
+                root_value=root_value, sims=done, **more)
 
 
 def oracle_positions(n_games, plies, sims, eval_fn=None, seed0=42):

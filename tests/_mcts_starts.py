@@ -12,6 +12,7 @@ import numpy as np
 
 from oracle import oracle as O
 
+from tests import _eval_cache as EC
 from tests import _mcts_arena as AR
 from tests import _mcts_search as S
 from tests import _mcts_selfplay_leaves as SL
@@ -232,3 +233,34 @@ def recycled_after(games, slots):
 SEED, N_GAMES, SIMS, SLOTS_THIRD = 202, 2 * len(NAMES), 16, 13
 GENERAL = {"reason2+", "reason2-", "reason3@1+", "reason3@0", "reason2@0", "reason4@1", "reason4@2+", "reason1+",
            "reason1-", "reason0", "root>64", "root>96", "root>128", "max@64+", "promo", "ep", "castle"}
+
+# The evaluation cache under recycling (tests/test_eval_cache_cpu.py, tests/test_eval_cache_gpu.py): the first 22
+# games of the set at 2 leaves on 2 slots, so that 20 games start in a recycled slot while the table is warm -- game
+# 19 starts from game 0's position. On 2 slots no two slots of this run are freed in the same ply-step, so the
+# slot every game sits in (and with it the order of a step's list) does not depend on the order in which freed
+# slots draw their ids; tests/test_eval_cache_cpu.py asserts that, a hit across games and a claim contest.
+RECYCLE = dict(n_games=22, slots=2, leaves=2, small=64, large=1 << 12)
+
+
+def recycling_seating():
+    """(starts, slot_of, ties) of the RECYCLE run, from the uncached restatement's games."""
+    ref = leaves_run(SEED, N_GAMES, SIMS, RECYCLE["leaves"])[:RECYCLE["n_games"]]
+    return EC.seating([r["holds"] for r in ref], RECYCLE["slots"])
+
+
+def recycling_run(entries, table=None):
+    """The RECYCLE run behind tests/_eval_cache.py's cache of `entries` entries (table: another table object in
+    its place) -> (games, info, the CachedEval)."""
+    n = RECYCLE["n_games"]
+    starts, slot_of, _ = recycling_seating()
+    cache = EC.CachedEval(EC._hash_many, entries, 0)
+    if table is not None:
+        cache.table = table
+    games, info = EC.play_many_cached([SEED + g for g in range(n)], list(range(n)), SIMS, [None] * n,
+                                      RECYCLE["leaves"], cache, c_puct=C_PUCT, eps=EPS, alpha=ALPHA,
+                                      per_game=[dict(start=start_of(g), max_moves=MAX_MOVES) for g in range(n)],
+                                      starts=starts, slot_of=slot_of)
+    return games, info, cache
+
+
+cached_recycling_run = functools.lru_cache(maxsize=None)(recycling_run)

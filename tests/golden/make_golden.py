@@ -21,6 +21,9 @@ Fixtures written next to this script (data only; no reference source):
                     eval batch sizes, per-ply choice margins
                     (scripts/self_play.py:111-255)
   unittests.json G5 the reference unittest scenarios, restated as data
+  attacks.npz       squareUnderAttack(r, c) on all 64 squares (bit r * 8 + c of one uint64 per state) for the
+                    states already in movegen.npz and movegen_wide.npz, before and after getValidMoves;
+                    `--attacks-only` reads those two files, regenerates nothing and writes this file alone
 """
 from __future__ import annotations
 
@@ -645,12 +648,47 @@ def gen_unittests(ce):
     return cases
 
 
+def gen_attacks(ce):
+    """The reference's squareUnderAttack on every square of every state recorded in movegen.npz and
+    movegen_wide.npz (read, not regenerated): the whole attack set, where those files hold one bit of it
+    (in_check). Equal states are asked once."""
+    from tests import _attack_classes as AC
+    gs = ce.GameState()
+    seen, out, total = {}, {}, {}
+    for name, key in (("movegen", "states"), ("movegen", "post_states"), ("movegen_wide", "states"),
+                      ("movegen_wide", "post_states")):
+        states = np.load(os.path.join(HERE, name + ".npz"))[key]
+        att = np.zeros(len(states), dtype=np.uint64)
+        for i, v in enumerate(states):
+            k = v.tobytes()
+            if k not in seen:
+                set_state(gs, v)
+                bits = 0
+                for sq in range(64):
+                    if gs.squareUnderAttack(sq // 8, sq % 8):
+                        bits |= 1 << sq
+                assert np.array_equal(state_vec(gs), v)  # the probes leave the position as it was
+                seen[k] = bits
+            att[i] = seen[k]
+        out[f"{name}_{'post' if key == 'post_states' else 'pre'}"] = att
+        counts = AC.count_classes(states, att)
+        print(name, key, len(states), "states,", len(seen), "distinct so far;", counts)
+        for c, n in counts.items():
+            total[c] = total.get(c, 0) + n
+    # the recorded states hold every class targets() special-cases (else: add hand-set states here)
+    assert all(total[c] > 0 for c in AC.CLASSES), {c: n for c, n in total.items() if n == 0}
+    return out
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     nn_only = "--nn-only" in sys.argv  # regenerate nn.npz from the committed movegen.npz positions
     wide_only = "--wide-only" in sys.argv  # write movegen_wide.npz alone; every other fixture stays as it is
     ref = args[0] if args else "/root/reference"
     sp, ce, ref_model, ref_ai = import_reference(ref)
+    if "--attacks-only" in sys.argv:  # reads movegen.npz and movegen_wide.npz as they are
+        np.savez_compressed(os.path.join(HERE, "attacks.npz"), **gen_attacks(ce))
+        return
     if wide_only:
         np.savez_compressed(os.path.join(HERE, "movegen_wide.npz"), **gen_movegen_wide(ce))
         return
@@ -684,6 +722,7 @@ def main():
     with open(os.path.join(HERE, "unittests.json"), "w") as f:
         json.dump(gen_unittests(ce), f)
     np.savez_compressed(os.path.join(HERE, "movegen_wide.npz"), **gen_movegen_wide(ce))
+    np.savez_compressed(os.path.join(HERE, "attacks.npz"), **gen_attacks(ce))
     print("done")
 
 

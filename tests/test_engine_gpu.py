@@ -129,6 +129,22 @@ def test_device_attacks_match_reference_in_check_wide(wide):
     assert got.tolist() == chk.tolist()
 
 
+@pytest.mark.parametrize("which", range(4))
+def test_device_attacks_match_reference_on_every_bit(golden_dir, which):
+    """kv_dev_attacks against tests/golden/attacks.npz: the reference's squareUnderAttack on all 64 squares of
+    every state of movegen.npz and movegen_wide.npz, before and after getValidMoves -- pawn pushes as attacks,
+    pawn diagonals only onto pieces or the en-passant square, castle destinations, files a and h
+    (tests/test_attacks_cpu.py asserts that the fixture holds each of those, and compares the host build)."""
+    from tests._attack_classes import differing, recorded
+    name, states, want = recorded(golden_dir)[which]
+    got = np.zeros(len(states), dtype=np.uint64)
+    _lib.check(_lib.lib().kv_dev_attacks(0, _p(states, C.c_int8), len(states), _p(got, C.c_uint64)), "kv_dev_attacks")
+    assert np.array_equal(got, want), f"{name}: {differing(got, want)}"
+    host = np.zeros(len(states), dtype=np.uint64)
+    _lib.check(_lib.lib().kv_host_attacks(_p(states, C.c_int8), len(states), _p(host, C.c_uint64)), "kv_host_attacks")
+    assert np.array_equal(got, host)
+
+
 def test_device_valid_moves_cap_contract(wide):
     """A list longer than `cap`: n_moves is -n, the first cap words are the uncapped list's, and the state after
     and inCheck do not depend on cap. Ten wide positions and the initial one, cap below, at and above 64."""

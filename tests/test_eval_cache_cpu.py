@@ -154,3 +154,73 @@ def test_the_runs_hold_the_cases_the_gpu_comparison_needs():
     assert tot[64]["reprobed"] > 0  # 64 entries: an evicted key is probed again later
     assert EC.RUNS["tail"]["n_games"] == EC.RUNS["tail"]["slots"] == 18  # no run recycles a slot
     assert all(cfg["n_games"] == cfg["slots"] for cfg in EC.RUNS.values())
+
+
+# ---- recycling: more games than slots (tests/_mcts_starts.RECYCLE)
+class _Unbounded(EC.Table):
+    """A dictionary in the table's place: every key its own entry, nothing ever replaced."""
+
+    def __init__(self):
+        super().__init__(0)
+        self.entries, self.slot = 1, {}
+
+    def index(self, key):
+        return key
+
+    def probe(self, key):
+        self.probes += 1
+        if len(key[1]) <= EC.CACHE_MAXM and key in self.slot:
+            self.hits += 1
+            return self.slot[key]
+        return None
+
+    def store(self, key, payload):
+        self.slot[key] = payload
+        self.stores += 1
+
+
+def _moves_of(games):
+    return [[x["move"] for x in g] for g in games], [[x["visits"] for x in g] for g in games]
+
+
+def test_recycling_the_cached_driver_plays_the_uncached_games():
+    from tests import _mcts_starts as ST
+    cfg = ST.RECYCLE
+    n, slots = cfg["n_games"], cfg["slots"]
+    ref = ST.leaves_run(ST.SEED, ST.N_GAMES, ST.SIMS, cfg["leaves"])[:n]
+    starts, slot_of, ties = ST.recycling_seating()
+    assert ties == 0  # no two slots freed in one ply-step: the seating is the device's, whatever its atomics do
+    assert starts == SL.starts_of([r["plies"] for r in ref], slots, [r["holds"] for r in ref])
+    assert slot_of[:slots] == list(range(slots)) and set(slot_of) == set(range(slots)) and max(starts) > 100
+    # the sim-steps of a ply-step are those of its slowest game
+    per_step = {}
+    for r, t0 in zip(ref, starts):
+        for p, k in enumerate(r["steps"]):
+            per_step[t0 + p] = max(per_step.get(t0 + p, 0), k)
+    for entries in (cfg["small"], cfg["large"]):
+        games, info, cache = ST.cached_recycling_run(entries)
+        assert _moves_of(games) == ([r["moves"] for r in ref], [r["visits"] for r in ref]), entries
+        assert [g.result for g in games] == [(r["plies"], r["outcome"], r["reason"], r["reward"]) for r in ref]
+        t = cache.table
+        assert t.probes == sum(info["pending"]) == sum(r["n_evals"] - r["plies"] for r in ref)
+        assert 0 < t.hits < t.probes and t.hits + t.stores <= t.probes and info["steps"] == sum(per_step.values())
+        print(f"entries {entries}: probes / hits / stores {t.probes} / {t.hits} / {t.stores}, contests "
+              f"{cache.contests}, hits on another game's entry {sum(a != b for a, b in cache.hits_from)}")
+        assert cache.contests >= 1  # two misses of one step on one entry: the earlier in slot order is stored
+    # the large table: a game in a recycled slot hits an entry that an earlier game stored
+    late = [(a, b) for a, b in ST.cached_recycling_run(cfg["large"])[2].hits_from if a >= slots and b < a]
+    assert late and (19, 0) in late  # game 19 starts where game 0 started
+    assert ST.cached_recycling_run(cfg["small"])[0] is not ST.cached_recycling_run(cfg["large"])[0]
+
+
+def test_recycling_hits_against_an_unbounded_dictionary():
+    """A table large enough that no probed key had been replaced counts the dictionary's hits."""
+    from tests import _mcts_starts as ST
+    games, info, big = ST.recycling_run(1 << 24)
+    again, info_d, model = ST.recycling_run(0, table=_Unbounded())
+    assert _moves_of(games) == _moves_of(again) and info == info_d
+    assert big.table.evicted_reprobed == 0
+    assert (big.table.probes, big.table.hits) == (model.table.probes, model.table.hits)
+    print(f"probes / hits {model.table.probes} / {model.table.hits}, keys {len(model.table.slot)}")
+    assert model.table.hits > 100 and sum(a != b for a, b in model.hits_from) > 0
+    assert big.hits_from == model.hits_from

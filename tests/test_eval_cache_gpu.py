@@ -325,3 +325,51 @@ def test_play_match_and_the_loop_take_eval_cache():
     assert stats[0]["arena"]["games"] == 6
     assert selfplay_shard.last_stats["cache_hits"] > 0
     assert selfplay_shard.last_stats["cache_probes"] == selfplay_shard.last_stats["leaf_rows_pending"]
+
+
+# ---- recycling: more games than slots while the table is warm (tests/_mcts_starts.RECYCLE)
+@functools.lru_cache(maxsize=None)
+def _recycling_run(entries):
+    from tests import _mcts_starts as ST
+    cfg = ST.RECYCLE
+    with SelfPlayEngine(synthetic_state_dict(42, "init"), slots=cfg["slots"], n_games=cfg["n_games"], seed=ST.SEED,
+                        max_moves=ST.MAX_MOVES, sims=ST.SIMS, c_puct=ST.C_PUCT, eps=ST.EPS, alpha=ST.ALPHA,
+                        keep_root_moves=True, leaves=cfg["leaves"], eval_cache=entries, eval_mode=EVAL_HASH) as eng:
+        eng._set_starts(ST.start_list())
+        eng.run()
+        return eng.records(), eng.root_visits(), eng.root_moves(), eng.games(), eng.stats()
+
+
+@pytest.mark.parametrize("size", ["small", "large"])
+def test_recycled_slots_find_the_finished_games_entries(size):
+    """22 games from the start set on 2 slots: a game that starts in a recycled slot probes a table that holds the
+    finished games' entries, and the slot it sits in decides who wins a contested entry. The games are those of
+    the run without the cache byte for byte, the three counters the restatement's with its rows in slot order
+    (tests/test_eval_cache_cpu.py: the seating is unambiguous, a later game hits an earlier game's entry in the
+    large table, entries are contested in both). The game table is compared with the
+    run without the cache only."""
+    from tests import _mcts_starts as ST
+    entries = ST.RECYCLE[size]
+    off, on = _recycling_run(0), _recycling_run(entries)
+    for k, part in enumerate(PARTS[:3]):
+        assert on[k].tobytes() == off[k].tobytes(), part
+    assert np.array_equal(np.sort(on[3], order="game_id"), np.sort(off[3], order="game_id")), PARTS[3]
+    assert len(on[3]) == ST.RECYCLE["n_games"]
+    for key in ("plies", "sims", "nn_rows", "leaf_rows_pending", "sim_steps", "games_done"):
+        assert on[4][key] == off[4][key], key
+    games, info, cache = ST.cached_recycling_run(entries)
+    recs = on[0]
+    for g, p in enumerate(games):
+        sel = recs["game_id"] == g
+        assert recs["move"][sel].tolist() == [x["move"] for x in p], g
+        assert sel.sum() == len(p) and [v[v >= 0].tolist() for v in on[1][sel]] == [x["visits"] for x in p], g
+        assert [bytes(b) for b in recs["board"][sel]] == [e["board"] for e in p.extra], g
+        assert [w[w != 0xffff].tolist() for w in on[2][sel]] == [x["words"] for x in p], g
+    t = cache.table
+    st = on[4]
+    print(f"eval_cache {entries} on {ST.RECYCLE['slots']} slots: probes / hits / stores {st['cache_probes']} / "
+          f"{st['cache_hits']} / {st['cache_stores']} (restated {t.probes} / {t.hits} / {t.stores}), contests "
+          f"{cache.contests}, hits on another game's entry {sum(a != b for a, b in cache.hits_from)}")
+    assert (st["cache_probes"], st["cache_hits"], st["cache_stores"]) == (t.probes, t.hits, t.stores)
+    assert st["sim_steps"] == info["steps"] and st["leaf_rows_pending"] == t.probes
+    assert (off[4]["cache_probes"], off[4]["cache_hits"], off[4]["cache_stores"]) == (0, 0, 0)

@@ -522,24 +522,22 @@ int kv_dev_py_random(int device, const uint64_t* seeds, int n, int count, double
  * kernel: M [100][rows][512] (digits 5: KV_PREC_I8X5's fp64 M; 4: the fp32
  * domain's (KV_ALGO_WINOGRAD88_I8) fp32 M, widened); v_digits (5 digits: planes
  * [100][K/32][5][rows][32]; 4 digits: row lines [100][K/32][rows][4][32]) and
- * v_exp [100][rows] (either may be NULL) return V's digits and row exponents. seg 1 (4 digits, K 512):
- * V's exponents per 256-channel segment (v_exp [100][2][rows]), the fp32 tower's A/B form. seg 2 (4 digits):
+ * v_exp [100][rows] (either may be NULL) return V's digits and row exponents. seg 2 (4 digits):
  * KV_PREC_I8R4's 4 radix-256 digits in row lines [100][K/32][rows][4][32], its GEMM and fp64 M. seg 3
  * (4 digits): KV_ALGO_WINOGRAD88_I8R3's 3 radix-256 digits in 96-byte row lines [100][K/32][rows][3][32] (the
- * first 3/4 of v_digits, the rest zero), the product's 6-pair GEMM and fp32 M. */
+ * first 3/4 of v_digits, the rest zero), the product's 6-pair GEMM and fp32 M. seg 1 (exponents per
+ * 256-channel segment, a removed form) and any other value: KV_EINVAL, checked before any device call. */
 int kv_dev_wino88i(int device, const double* V, int rows, const double* U, int K, int digits, int seg, double* M,
                    int8_t* v_digits, int* v_exp);
 /* The fp32 tower's residual output kernel on int8 digits (KV_ALGO_WINOGRAD88_I8): M [100][rows][512] fp32
  * (rows a multiple of 128), folded BN scale / shift [512], resid [rows][64][512] or NULL -> Y
  * [rows][64][512] (= ReLU(A^T M A * scale + shift (+ resid))) and the next conv's V as row-line digits
  * [100][16][rows][4][32] with row exponents [100][rows]. fused bit 0 set: the product's one-kernel form
- * (KV_I8F32_OUT's choice; with bit 3 also set the 64-register wino88i32_out2_kernel, with bit 5 the
- * persistent LDS-DMA wino88i32_outp_kernel; bit 4: 3 radix-256 digits, KV_ALGO_WINOGRAD88_I8R3's, in 96-byte
- * lines [100][16][rows][3][32] in the first 3/4 of v_digits, the rest zero), clear:
- * wino88_out_kernel's fp32 V then the slice kernel (bit-identical); bit 1:
- * exponents per 256-channel segment ([100][2][rows]) instead of per row; bit 2 (KV_ALGO_WINOGRAD88_I8V's V,
- * per row): with bit 0 the one-kernel wino88i32v_out_kernel, without it wino88_out_kernel's Y, then
- * wino88d_in_kernel's fp64 V and the slice kernel (bit-identical). */
+ * (wino88i32_out_kernel), clear: wino88_out_kernel's fp32 V then the slice kernel (bit-identical); bit 4: 3
+ * radix-256 digits, KV_ALGO_WINOGRAD88_I8R3's, in 96-byte lines [100][16][rows][3][32] in the first 3/4 of
+ * v_digits, the rest zero; bit 2 (KV_ALGO_WINOGRAD88_I8V's V, not with bit 4): with bit 0 the one-kernel
+ * wino88i32v_out_kernel, without it wino88_out_kernel's Y, then wino88d_in_kernel's fp64 V and the slice kernel
+ * (bit-identical). Bits 1, 3 and 5 (removed forms) and higher: KV_EINVAL, checked before any device call. */
 int kv_dev_wino88i32_out(int device, const float* M, int rows, const float* scale, const float* shift,
                          const float* resid, int fused, float* Y, int8_t* v_digits, int* v_exp);
 /* The front of the R3 tower (KV_ALGO_WINOGRAD88_I8R3): boards [nb][64] int8 piece codes (0 empty, 1-12), `rows`
@@ -573,11 +571,6 @@ int kv_dev_wino88r_out(int device, const double* M, int rows, const float* scale
  * so b runs half a layer behind a; the caller enqueues a's forward first, then b's. Outputs are unchanged. A
  * destroyed `a` must not stay b's leader: pair again (follow 0) or destroy b first. */
 int kv_dev_net_pair(kv_net* a, kv_net* b, int cu_share, int follow);
-/* Timing / A-B harness of the fp32 tower's int8-digit GEMM on seeded random digits (rows boards, K 256 or
- * 512): variant 0 the round-4 kernel, 1.. round-5 forms (persistent / per-tile, k per stage, ring depth);
- * avg_us = mean HIP-event time of `iters` launches; M_out [100][rows][512] (optional) for a bit-for-bit
- * comparison of the variants. */
-int kv_dev_i8gemm_bench(int device, int rows, int K, int variant, int iters, float* avg_us, float* M_out);
 /* The clock the chip holds under the headline GEMM (a diagnostic; MI355X_MICROARCH.md "DVFS give-back" item 6):
  * the product's fp32-tower GEMM (K 512, `rows` boards, `digits` 4 or 3 (KV_ALGO_WINOGRAD88_I8R3), seeded random
  * digits) back to back for `seconds`, then

@@ -154,7 +154,6 @@ def _declare(L):
                                P(C.c_int32), P(C.c_uint32), P(C.c_uint32), P(i64)], i),
         "kv_host_libm": ([i, P(C.c_double), P(C.c_double), i, P(C.c_double)], i),
         "kv_dev_wino88i": ([i, P(C.c_double), i, P(C.c_double), i, i, i, P(C.c_double), P(C.c_int8), P(i)], i),
-        "kv_dev_i8gemm_bench": ([i, i, i, i, i, P(C.c_float), P(C.c_float)], i),
         "kv_dev_gemm_clock": ([i, i, i, C.c_double, P(C.c_double)], i),
         "kv_dev_r3gemm_clock": ([i, i, i, i, C.c_double, P(C.c_double)], i),
         "kv_dev_wino88i_r3": ([i, P(C.c_double), i, P(C.c_double), i, i, i, i, i, P(C.c_double), P(i64)], i),
@@ -207,7 +206,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_load_weights", "kv_load_weights_b", "kv_engine_calibration_b", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_sizeof_config", "kv_sizeof_stats", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
             "kv_search", "kv_sizeof_search_result", "kv_search_advance", "kv_search_continue", "kv_search_tree_size",
             "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_set_starts", "kv_dev_attacks", "kv_host_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm", "kv_dev_eval_cache",
-            "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_tower_front", "kv_dev_tower_back", "kv_dev_i8gemm_bench",
+            "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_tower_front", "kv_dev_tower_back",
             "kv_dev_gemm_clock", "kv_dev_r3gemm_clock", "kv_dev_wino88i_r3", "kv_dev_out_phases", "kv_dev_net_pair",
             "kv_pgn_extract", "kv_fen_codes", "kv_san_move_index", "kv_chess_perft", "kv_chess_san", "kv_chess_fen",
             "kv_tr_conv3x3_f16", "kv_tr_conv3x3_add_f16", "kv_tr_conv_weights_f16", "kv_tr_wgrad_workspace", "kv_tr_conv3x3_wgrad_f16",

@@ -974,8 +974,7 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
         ALLOC(e->sqrt_tab, (size_t)(t.ncap + 2) * sizeof(float));
         if (cfg->keep_root_visits) ALLOC(t.root_visits, (size_t)e->cfg.record_cap * kv::MAXM * sizeof(uint16_t));
         if (cfg->keep_root_visits == 2) ALLOC(t.root_moves, (size_t)e->cfg.record_cap * kv::MAXM * sizeof(uint16_t));
-        const char* mc_env = getenv("KV_MCTS_COMPACT");  // "0": always the full-slot leaf batch (A/B timing)
-        if (cfg->eval_mode != KV_EVAL_HASH && S > 1 && !(mc_env && mc_env[0] == '0')) {
+        if (cfg->eval_mode != KV_EVAL_HASH && S > 1) {
             ALLOC(e->mc_slot_of, S * sizeof(int));
             ALLOC(e->mc_row_of, S * sizeof(int));
             ALLOC(e->mc_boards, S * 64);

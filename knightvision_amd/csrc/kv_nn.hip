@@ -387,7 +387,7 @@ __global__ __launch_bounds__(1024) void wino88_out_heads_kernel(
     const int c = w * 32 + (lane & 31), b = blockIdx.x;
     {
         float x2[4][8];  // pixels (4h + ii, j) of channel c
-        wino88_out_plane_half<true, false, false, 0, YNT>(M, rows, b, c, h, scale[c], shift[c], resid, nullptr, x2);
+        wino88_out_plane_half<true, false, YNT>(M, rows, b, c, h, scale[c], shift[c], resid, nullptr, x2);
 #pragma unroll
         for (int ii = 0; ii < 4; ++ii)
 #pragma unroll
@@ -617,7 +617,8 @@ __global__ void planes_to_nhwc16_kernel(const float* __restrict__ planes, int nb
 //   KV_PATH_WINO88_I8F32V the same with fp64 input transforms (V cut to digits from fp64)
 //   KV_PATH_WINO88_I8R F(8x8), fp64 Winograd domain, GEMMs on 4 radix-256 digits (13 of 16 pairs)
 //   KV_PATH_WINO88_I8F32R3 F(8x8), fp32 Winograd domain, GEMMs on 3 radix-256 digits (6 of 9 pairs)
-// fp32 + KV_ALGO_AUTO picks its paths per weight load (kv_net_calibration).
+// fp32 + KV_ALGO_AUTO picks its paths per weight load (kv_net_calibration). A path is chosen by precision, algo
+// and batch alone: nothing here reads the environment, and each path has one kernel form per batch class.
 constexpr int kNPath = KV_NPATH;
 
 struct kv_net {
@@ -749,32 +750,6 @@ static hipError_t lds_opt_in(const void* fn, int bytes) {
 }
 
 // CUs of the current device, cached per device (the F(8x8) point split reads it per launch)
-// KV_OUT_STAG: the output kernels' phase stagger (kv_wino88i.h out_stagger), in units of s_sleep 127
-// KV_R3_ONEROUND=0: the R3 GEMM's TPW-tile groups one per workgroup, in rounds (the A/B form)
-static bool r3_one_round() {
-    static const bool v = [] {
-        const char* e = getenv("KV_R3_ONEROUND");
-        return !e || e[0] != '0';
-    }();
-    return v;
-}
-
-static int out_abl() {  // KV_OUT_ABL: output-kernel timing ablations (A/B tooling only; outputs invalid)
-    static const int v = [] {
-        const char* e = getenv("KV_OUT_ABL");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-
-static int out_stag() {
-    static const int v = [] {
-        const char* e = getenv("KV_OUT_STAG");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-
 static int device_cus() {
     static std::mutex mu;
     static int cus[64] = {};
@@ -868,7 +843,7 @@ static int net_reserve(kv_net* net, int nb_pad) {
     KV_HIP(hipMalloc(&net->X, (size_t)cap * 64 * 512 * 4));
     KV_HIP(hipMalloc(&net->T, (size_t)cap * 64 * 512 * 4));
     KV_HIP(hipMalloc(&net->pfeat, (size_t)cap * 128 * 4));
-    KV_HIP(hipMalloc(&net->ev8, (size_t)cap * kv::W88_XI * 2 * sizeof(int)));  // 2: segment exponents
+    KV_HIP(hipMalloc(&net->ev8, (size_t)cap * kv::W88_XI * sizeof(int)));
     KV_HIP(hipMalloc(&net->evmax8, (size_t)cap * kv::W88_XI * sizeof(unsigned)));
     if (!net->slab)  // 48 splits x 16 boards x 64 px x 512 channels
         KV_HIP(hipMalloc(&net->slab, (size_t)(144 / kSplitKt) * kSplitMaxBoards * 64 * 512 * 4));
@@ -895,16 +870,6 @@ static int launch_wino_gemm_t(const float* V, const float* U, float* M, int rows
     return KV_OK;
 }
 
-// KV_DEBUG_SKIP_TRANSFORMS=1: the Winograd towers' output/input transform launches are skipped (timing
-// probe only: the GEMM-only forward bounds what fusing the transforms away could gain; outputs invalid)
-static bool debug_skip_transforms() {
-    static const int v = [] {
-        const char* e = getenv("KV_DEBUG_SKIP_TRANSFORMS");
-        return e && e[0] == '1' ? 1 : 0;
-    }();
-    return v != 0;
-}
-
 // F(8x8) GEMMs (100 points, rows = 1 per board, a multiple of 64): 128x128 tiles when the
 // rows allow, else 64x128; same k order, same bits
 // Round filling: the 128x128 tiles of the first points fill whole rounds of the resident
@@ -916,7 +881,7 @@ static bool debug_skip_transforms() {
 // -> 5.31 ms. At 2,048 boards the last round is one tile per CU, which the half tiles do
 // not beat (10.25 vs 10.32 ms), so it stays one launch; nor do 64x64 or 128x64 tiles for its last
 // 4 points (10.42-10.49 vs 10.39-10.42 ms, profiles/r03_w88_tail_ab.log). Same k order, same bits
-// (profiles/r03_w88split_ab.log). KV_W88_SPLIT=0 turns it off. The split launch deals its grid in
+// (profiles/r03_w88split_ab.log). The split launch deals its grid in
 // XCD groups of 8, so both parts must be multiples of 8 workgroups; otherwise one launch.
 // (Measured and dropped, round 4: the 256-board layer as 96 points of 128x128 tiles with k-tiles of 16 at
 // 3 workgroups per CU -- exactly one round -- plus the last 4 points as 32x128 or 32x64 tiles: 112.7 +
@@ -925,12 +890,8 @@ static bool debug_skip_transforms() {
 // CU -- every workgroup's first k-tile load and its M epilogue are exposed -- against ~134 in the 12.5
 // rounds of C3.)
 static int wino88_split_points(int rows) {
-    static const int mode = [] {  // thread-safe one-time initialisation
-        const char* e = getenv("KV_W88_SPLIT");
-        return e ? atoi(e) : 1;
-    }();
     const int cus = device_cus();
-    if (!mode || cus <= 0) return kv::W88_XI;
+    if (cus <= 0) return kv::W88_XI;
     const int per_xi = (rows / 128) * 4, slots = 2 * cus;
     const int rem = (kv::W88_XI * per_xi) % slots;  // tiles of the last round
     if (rem % cus == 0) return kv::W88_XI;           // whole rounds, or one tile on every CU
@@ -982,12 +943,6 @@ static int wino88_blocks(kv_net* net, int nb, bool mark, hipStream_t st) {
     float* M = (float*)net->Mw;
     float* V256 = (float*)net->V256;
     int rc;
-    if (debug_skip_transforms()) {
-        if ((rc = launch_wino88_gemm<256>(V256, net->U88 + net->uoff88[1], M, rows, stride, st))) return rc;
-        for (int l = 2; l < 12; ++l)
-            if ((rc = launch_wino88_gemm<512>(V, net->U88 + net->uoff88[l], M, rows, stride, st))) return rc;
-        return KV_OK;
-    }
     if ((rc = launch_wino88_gemm<256>(V256, net->U88 + net->uoff88[1], M, rows, stride, st))) return rc;
     if ((rc = launch_wino88_out<false, true, true>(net, 1, M, nb, stride, nullptr, net->X, V, st))) return rc;
     if (mark && net->timing) KV_HIP(hipEventRecord(net->ev[1], st));
@@ -1071,56 +1026,14 @@ static int wino88d_blocks(kv_net* net, int nb, bool mark, hipStream_t st) {
 // ---- F(8x8) on int8 digits (kv_wino88i.h): the fp64 tower's transforms, V64 sliced into digits
 // before each GEMM ----
 // (4 digits: the fp32 domain's row-line layout)
-// (NSEG 2: V's exponents per 256-channel segment, K 512 only)
 // (R8: KV_PATH_WINO88_I8R's 4 radix-256 digits of fp64 rows, row lines)
 // (R3: KV_PATH_WINO88_I8F32R3's 3 radix-256 digits in 96-byte row lines)
-template <int K, int D = kv::kI8Digits, class T, int NSEG = 1, bool R8 = false, bool R3 = false>
+template <int K, int D = kv::kI8Digits, class T, bool R8 = false, bool R3 = false>
 static int launch_wino88i_slice(const T* src, int n, int slab_rows, int nslab, int8_t* dst, int* ex,
                                 hipStream_t st) {
     const int waves = n * nslab;
-    hipLaunchKernelGGL((kv::wino88i_slice_kernel<K, T, D, D == kv::kI8DigitsF32, NSEG, R8, R3>),
+    hipLaunchKernelGGL((kv::wino88i_slice_kernel<K, T, D, D == kv::kI8DigitsF32, R8, R3>),
                        dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, src, n, slab_rows, nslab, dst, ex);
-    KV_HIP(hipGetLastError());
-    return KV_OK;
-}
-
-// 128 x 128 tiles only (net_pad rounds this path's batch up to 128 boards)
-// KV_I8_SPREAD=0 (timing probe): a stage's copies issued together after the barrier
-static bool i8_spread() {
-    static const bool v = [] {
-        const char* e = getenv("KV_I8_SPREAD");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
-template <int K, int D = kv::kI8Digits, class OutT = double>
-static int launch_wino88i_gemm(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, OutT* M, int rows,
-                               int stride, hipStream_t st) {
-    using T = kv::Wino88iTile<D>;
-    constexpr bool RL = D == kv::kI8DigitsF32;  // 4 digits: row lines
-    auto kern = i8_spread() ? kv::wino88i_gemm_kernel<K, D, true, OutT, RL> : kv::wino88i_gemm_kernel<K, D, false, OutT, RL>;
-    KV_HIP(lds_opt_in((const void*)kern, (int)T::BYTES));
-    const int nwg = kv::W88_XI * (rows / T::WM) * (512 / T::WN);
-    KV_REQUIRE(rows % T::WM == 0 && stride % T::WM == 0 && nwg % 8 == 0, KV_EINVAL,
-               "wino gemm i8: rows %d / stride %d vs tile %d", rows, stride, T::WM);
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(T::THREADS), T::BYTES, st, V8, ev, U8, eu, M, rows, 512, stride);
-    KV_HIP(hipGetLastError());
-    return KV_OK;
-}
-
-// the fp32 tower's int8-digit GEMM with the stage barrier in the middle of the stage (wino88i32_gemm_mid_kernel)
-template <int K>
-static int launch_wino88i32_gemm_mid(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, float* M,
-                                     int rows, int stride, hipStream_t st) {
-    using T = kv::Wino88iTile<kv::kI8DigitsF32>;
-    constexpr int bytes = 4 * T::STAGE;
-    KV_HIP(lds_opt_in((const void*)kv::wino88i32_gemm_mid_kernel<K>, bytes));
-    const int nwg = kv::W88_XI * (rows / T::WM) * (512 / T::WN);
-    KV_REQUIRE(rows % T::WM == 0 && stride % T::WM == 0 && nwg % 8 == 0, KV_EINVAL,
-               "wino gemm i8 (mid): rows %d / stride %d vs tile %d", rows, stride, T::WM);
-    hipLaunchKernelGGL(kv::wino88i32_gemm_mid_kernel<K>, dim3(nwg), dim3(T::THREADS), bytes, st, V8, ev, U8, eu, M,
-                       rows, 512, stride);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
@@ -1141,17 +1054,17 @@ static int launch_wino88i_gemm_lag5(const int8_t* V8, const int* ev, const int8_
     return KV_OK;
 }
 
-// the lagging-half form (wino88i32_gemm_lag_kernel); STAG: only waves 0-3 lag
-template <int K, bool STAG, int LJ = 2>
+// the lagging-half form (wino88i32_gemm_lag_kernel)
+template <int K>
 static int launch_wino88i32_gemm_lag(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, float* M,
                                      int rows, int stride, hipStream_t st) {
     using T = kv::Wino88iTile<kv::kI8DigitsF32>;
     constexpr int bytes = 3 * T::STAGE;
-    KV_HIP(lds_opt_in((const void*)kv::wino88i32_gemm_lag_kernel<K, STAG, LJ>, bytes));
+    KV_HIP(lds_opt_in((const void*)kv::wino88i32_gemm_lag_kernel<K>, bytes));
     const int nwg = kv::W88_XI * (rows / T::WM) * (512 / T::WN);
     KV_REQUIRE(rows % T::WM == 0 && stride % T::WM == 0 && nwg % 8 == 0, KV_EINVAL,
                "wino gemm i8 (lag): rows %d / stride %d vs tile %d", rows, stride, T::WM);
-    hipLaunchKernelGGL((kv::wino88i32_gemm_lag_kernel<K, STAG, LJ>), dim3(nwg), dim3(T::THREADS), bytes, st, V8, ev,
+    hipLaunchKernelGGL((kv::wino88i32_gemm_lag_kernel<K>), dim3(nwg), dim3(T::THREADS), bytes, st, V8, ev,
                        U8, eu, M, rows, 512, stride);
     KV_HIP(hipGetLastError());
     return KV_OK;
@@ -1162,12 +1075,12 @@ static int launch_wino88i32_gemm_lag(const int8_t* V8, const int* ev, const int8
 #ifndef KV_I8F32_NB
 #define KV_I8F32_NB 3
 #endif
-template <int K, int TPW, int ND = 4, int LJ = KV_I8F32_LJ, int NB = KV_I8F32_NB>
+template <int K, int TPW>
 static int launch_wino88i32_gemm_lagt(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, float* M,
                                       int rows, int stride, hipStream_t st) {
     using T = kv::Wino88iTile<kv::kI8DigitsF32>;
-    constexpr int bytes = NB * T::STAGE;
-    auto kern = kv::wino88i32_gemm_lagt_kernel<K, TPW, LJ, false, ND, NB>;
+    constexpr int bytes = KV_I8F32_NB * T::STAGE;
+    auto kern = kv::wino88i32_gemm_lagt_kernel<K, TPW, KV_I8F32_LJ, false, 4, KV_I8F32_NB>;
     KV_HIP(lds_opt_in((const void*)kern, bytes));
     const int tiles = kv::W88_XI * (rows / T::WM) * (512 / T::WN);
     KV_REQUIRE(rows % T::WM == 0 && stride % T::WM == 0 && tiles % (8 * TPW) == 0, KV_EINVAL,
@@ -1183,7 +1096,7 @@ static int launch_wino88i32_gemm_lagt(const int8_t* V8, const int* ev, const int
 // running across them (no prologue between them)
 static int r3k64_grid(int tiles, int tpw, int share) {
     const int nwg = tiles / tpw, cus = gemm_cus(share);
-    return r3_one_round() && cus > 0 && cus % 8 == 0 && nwg > cus && nwg % cus == 0 ? cus : nwg;
+    return cus > 0 && cus % 8 == 0 && nwg > cus && nwg % cus == 0 ? cus : nwg;
 }
 
 // R3's GEMM with 64-k stages (kv_wino88i.h wino88i32_gemm_r3k64_kernel): 3 x 48 KiB of LDS. force_nwg (the dev
@@ -1193,18 +1106,6 @@ static int launch_wino88i32_gemm_r3k64(const int8_t* V8, const int* ev, const in
                                        int rows, int stride, hipStream_t st, int share = 1, int force_nwg = 0) {
     constexpr int bytes = 3 * 4 * 128 * 96 + 2 * TPW * 1024;  // the ring + two groups' tile exponents
     auto kern = kv::wino88i32_gemm_r3k64_kernel<K, TPW>;
-    if constexpr (K == 512 && TPW == 5) {  // KV_R3K64_ABL: timing ablations (outputs invalid; A/B tooling only)
-        static const int abl = [] {
-            const char* e = getenv("KV_R3K64_ABL");
-            return e ? atoi(e) : 0;
-        }();
-        if (abl == 1) kern = kv::wino88i32_gemm_r3k64_kernel<K, TPW, false, 1>;
-        if (abl == 2) kern = kv::wino88i32_gemm_r3k64_kernel<K, TPW, false, 2>;
-        if (abl == 3) kern = kv::wino88i32_gemm_r3k64_kernel<K, TPW, false, 3>;
-        if (abl == 4) kern = kv::wino88i32_gemm_r3k64_kernel<K, TPW, false, 4>;
-        if (abl == 7) kern = kv::wino88i32_gemm_r3k64_kernel<K, TPW, false, 7>;
-        if (abl == 8) kern = kv::wino88i32_gemm_r3k64_kernel<K, TPW, false, 8>;
-    }
     KV_HIP(lds_opt_in((const void*)kern, bytes));
     const int tiles = kv::W88_XI * (rows / 128) * (512 / 128);
     KV_REQUIRE(rows % 128 == 0 && stride % 128 == 0 && tiles % (8 * TPW) == 0, KV_EINVAL,
@@ -1221,15 +1122,11 @@ static int launch_wino88i32_gemm_r3k64(const int8_t* V8, const int* ev, const in
 // t-tile workgroups in whole rounds -- is no more than the single-tile grid's ceil(tiles / CUs) (then the same
 // or fewer tile-times, and t - 1 of t prologues hidden), else 1. C3's 6,400 tiles on 256 CUs: 5 rounds of
 // 5-tile workgroups (25 tile-times either way: 497 vs 511 us); C2's 800: one round of 4-tile workgroups (4
-// tile-times either way: 72 vs 76 us). KV_I8F32_TPW=1: always one tile per workgroup.
+// tile-times either way: 72 vs 76 us).
 static int i8f32_tiles_per_wg(int rows, int share = 1) {
-    static const bool off = [] {
-        const char* e = getenv("KV_I8F32_TPW");
-        return e && e[0] == '1';
-    }();
     const int cus = gemm_cus(share);
     const int tiles = kv::W88_XI * (rows / 128) * 4;
-    if (off || cus <= 0) return 1;
+    if (cus <= 0) return 1;
     const int single = (tiles + cus - 1) / cus;
     for (int t = 5; t >= 4; --t) {
         if (tiles % (8 * t)) continue;
@@ -1237,28 +1134,6 @@ static int i8f32_tiles_per_wg(int rows, int share = 1) {
         if ((wgs + cus - 1) / cus * t <= single) return t;
     }
     return 1;
-}
-
-// the fp32 tower's int8-digit GEMM, round-5 form (kv_wino88i.h wino88i32_gemm_kernel): persistent
-// workgroups, one per CU (grid a multiple of 8, at most the tile count), or one tile each (persist false)
-template <int K, int KS, int NBUF, int NSEG = 1, int ABL = 0, bool DEFER = false>
-static int launch_wino88i32_gemm(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, float* M,
-                                 int rows, int stride, bool persist, hipStream_t st) {
-    using T = kv::I8G32<KS, NBUF>;
-    auto kern = kv::wino88i32_gemm_kernel<K, KS, NBUF, NSEG, ABL, DEFER>;
-    KV_HIP(lds_opt_in((const void*)kern, (int)T::BYTES));
-    const int ntiles = kv::W88_XI * (rows / T::WN) * (512 / T::WM);
-    KV_REQUIRE(rows % T::WN == 0 && stride % T::WN == 0 && ntiles % 8 == 0, KV_EINVAL,
-               "wino88i32 gemm: rows %d / stride %d vs tile %d", rows, stride, T::WN);
-    int grid = ntiles;
-    if (persist) {
-        const int cus = device_cus();
-        const int g = cus >= 8 ? (cus / 8) * 8 : 8;
-        grid = g < ntiles ? g : ntiles;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(T::THREADS), T::BYTES, st, V8, ev, U8, eu, M, rows, stride);
-    KV_HIP(hipGetLastError());
-    return KV_OK;
 }
 
 // conv l's output transform into Y (fp32), then the next conv's digit planes from Y (kv_wino88i.h); r8: 4
@@ -1282,17 +1157,11 @@ static int launch_wino88i_out(kv_net* net, int l, const double* M, int nb, int s
     return KV_OK;
 }
 
-// KV_PREC_I8X5's GEMM: wino88i_gemm_lag5_kernel (the lagging half; bit-identical); KV_I8X5_GEMM=r4: the
-// round-4 wino88i_gemm_kernel<K, 5>
+// KV_PREC_I8X5's GEMM: wino88i_gemm_lag5_kernel (the lagging half)
 template <int K>
 static int i8x5_gemm(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, double* M, int rows, int stride,
                      hipStream_t st) {
-    static const bool r4 = [] {
-        const char* e = getenv("KV_I8X5_GEMM");
-        return e && !strcmp(e, "r4");
-    }();
-    note_dom<K>(r4 ? "wino88i_gemm_kernel<512,5>" : "wino88i_gemm_lag5_kernel<512,3,5,7,false>");
-    if (r4) return launch_wino88i_gemm<K>(V8, ev, U8, eu, M, rows, stride, st);
+    note_dom<K>("wino88i_gemm_lag5_kernel<512,3,5,7,false>");
     return launch_wino88i_gemm_lag5<K>(V8, ev, U8, eu, M, rows, stride, st);
 }
 
@@ -1319,8 +1188,7 @@ static int launch_wino88i64r_out(kv_net* net, int l, const double* M, int nb, in
                                  float* Y, hipStream_t st) {
     const float* W = net->w;
     hipLaunchKernelGGL((kv::wino88i64r_out_kernel<RESID, WRITE_Y>), dim3(1, nb), dim3(1024), 0, st, M, stride,
-                       W + net->off.scale[l], W + net->off.shift[l], resid, Y, net->V8, net->ev8, out_stag(),
-                       device_cus());
+                       W + net->off.scale[l], W + net->off.shift[l], resid, Y, net->V8, net->ev8);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
@@ -1343,7 +1211,7 @@ static int wino88i_blocks(kv_net* net, int nb, bool mark, bool r8, hipStream_t s
     };
     int rc;
     // conv2: the stem wrote V64 (256 channels); its digits by the slice kernel
-    rc = r8 ? launch_wino88i_slice<256, 4, double, 1, true>((const double*)net->V256, rows, stride, kv::W88_XI, net->V8,
+    rc = r8 ? launch_wino88i_slice<256, 4, double, true>((const double*)net->V256, rows, stride, kv::W88_XI, net->V8,
                                                             net->ev8, st)
             : launch_wino88i_slice<256>((const double*)net->V256, rows, stride, kv::W88_XI, net->V8, net->ev8, st);
     if (rc) return rc;
@@ -1372,92 +1240,36 @@ static int wino88i_blocks(kv_net* net, int nb, bool mark, bool r8, hipStream_t s
 }
 
 // ---- the fp32 domain on int8 digits (KV_PATH_WINO88_I8F32): the fp32 F(8x8) tower's transforms; each
-// residual conv's output kernel (wino88i32_out_kernel) writes the next conv's V directly as row-line digits.
-// conv2's V256 (from the stem, 256 channels) goes through the slice kernel. Forms (read once from the
-// environment; A/B probes, the defaults are the measured fastest):
-//   KV_I8F32_SEG   0 (default): V's exponents per row (one 512-channel output workgroup per board); 1: per
-//                  256-channel segment -- the output kernel's workgroup is 256 channels of a board, two per
-//                  CU -- and the GEMM combines the two segments
-//   KV_I8F32_SLICE 1: wino88_out_kernel's fp32 V + the slice kernel (the round-4 form; the same digits)
-//   KV_I8F32_GEMM  default: wino88i32_gemm_lag_kernel (128x128 tiles, each stage's last 6 MFMAs per wave run
-//                  after the next barrier, under the next stage's first LDS reads: 6 % faster than the round-4
-//                  kernel, bit-identical, profiles/r05_i8gemm_lag_ab.log); r4: the round-4
-//                  wino88i_gemm_kernel; p: the persistent wino88i32_gemm_kernel (5 % slower than r4,
-//                  profiles/r05_i8gemm_variants.log). The segment form always runs wino88i32_gemm_kernel ----
-//   KV_I8F32_OUT   the output kernel (the same bits in every form): default the held-V one (wino88i32_out_kernel:
-//                  the next V's 50 values per lane held across the exponent barrier, one board per CU); r64:
-//                  wino88i32_out2_kernel (the 32 activations held, the transform run twice, 64 registers: two boards
-//                  per CU; 2-3 % slower forward, profiles/r06_out2_ab.log); p: wino88i32_outp_kernel (persistent,
-//                  M streamed through LDS by DMA two column steps ahead, across boards)
-struct I8f32Form {
-    bool seg = false, slice = false, r4 = false, persist = false;
-    int out = 0;  // 0 held, 1 r64, 2 persistent
-};
-static const I8f32Form& i8f32_form() {
-    static const I8f32Form f = [] {
-        I8f32Form x;
-        const char* e = getenv("KV_I8F32_SEG");
-        x.seg = e && e[0] == '1';
-        e = getenv("KV_I8F32_SLICE");
-        x.slice = e && e[0] == '1';
-        e = getenv("KV_I8F32_GEMM");
-        x.r4 = e && !strcmp(e, "r4") && !x.seg;
-        x.persist = e && !strcmp(e, "p");
-        e = getenv("KV_I8F32_OUT");
-        x.out = !e ? 0 : !strcmp(e, "r64") ? 1 : !strcmp(e, "p") ? 2 : 0;
-        return x;
-    }();
-    return f;
-}
-
-// the persistent output kernel (kv_wino88i.h wino88i32_outp_kernel): one workgroup per CU (at most one per
-// board), each looping over boards blockIdx.x + k gridDim.x; M's stride must be the board count (rows)
-template <bool RESID, bool WRITE_Y>
-static int launch_wino88i32_outp(const float* M, int nb, int stride, const float* sc, const float* sh,
-                                 const float* resid, float* Y, int8_t* V8, int* ev, hipStream_t st, bool r3) {
-    KV_REQUIRE(stride == nb, KV_EINVAL, "wino88i32_outp: M stride %d != boards %d", stride, nb);
-    const int cus = device_cus();
-    const int grid = cus > 0 && cus < nb ? cus : nb;
-    auto kern = r3 ? kv::wino88i32_outp_kernel<RESID, WRITE_Y, true> : kv::wino88i32_outp_kernel<RESID, WRITE_Y, false>;
-    KV_HIP(lds_opt_in((const void*)kern, kv::kOutpLds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), kv::kOutpLds, st, M, nb, sc, sh, resid, Y, V8, ev);
-    KV_HIP(hipGetLastError());
-    return KV_OK;
-}
+// residual conv's output kernel (wino88i32_out_kernel: the next V's 50 values per lane held across the exponent
+// barrier, one board per CU) writes the next conv's V directly as row-line digits under per-row exponents.
+// conv2's V256 (from the stem, 256 channels) goes through the slice kernel. The GEMM is
+// wino88i32_gemm_lagt_kernel (4 or 5 tiles per workgroup when they fill whole rounds, i8f32_tiles_per_wg) or
+// wino88i32_gemm_lag_kernel (one tile). The forms measured against these and removed -- the round-4 and round-5
+// GEMMs, the mid-barrier GEMM, per-segment exponents, the slice-form output step, the 64-register and the
+// persistent output kernels, the phase stagger -- are on record in DESIGN.md and profiles/ ----
 
 // r3: KV_PATH_WINO88_I8F32R3's digits (3 radix-256, per-row exponents)
 template <bool RESID, bool WRITE_Y>
 static int launch_wino88i32_out(kv_net* net, int l, const float* M, int nb, int stride, const float* resid,
-                                float* Y, int8_t* V8, int* ev, bool seg, hipStream_t st, bool r3 = false) {
+                                float* Y, int8_t* V8, int* ev, hipStream_t st, bool r3 = false) {
     const float* W = net->w;
-    const int cus = device_cus(), stag = out_stag();
     const float* sc = W + net->off.scale[l];
     const float* sh = W + net->off.shift[l];
-    const int form = i8f32_form().out;
     KV_REQUIRE(!r3 || nb % 32 == 0, KV_EINVAL, "R3 output kernel: %d boards (a multiple of 32: out_board)", nb);
-    if (seg)
-        hipLaunchKernelGGL((kv::wino88i32_out_kernel<RESID, WRITE_Y, 256>), dim3(2, nb), dim3(512), 0, st, M, stride,
-                           sc, sh, resid, Y, V8, ev, 0, 0);
-    else if (form == 2)
-        return launch_wino88i32_outp<RESID, WRITE_Y>(M, nb, stride, sc, sh, resid, Y, V8, ev, st, r3);
-    else if (form == 0 && r3 && out_abl() == 1)  // KV_OUT_ABL=1: timing ablation (outputs invalid)
-        hipLaunchKernelGGL((kv::wino88i32_out_kernel<RESID, WRITE_Y, 512, true, false, 1>), dim3(1, nb), dim3(1024), 0,
-                           st, M, stride, sc, sh, resid, Y, V8, ev, stag, cus);
-    else if (form == 0 && r3 && WRITE_Y && nb >= 1024)  // Y / residual non-temporal at large batches (YNT)
-        hipLaunchKernelGGL((kv::wino88i32_out_kernel<RESID, WRITE_Y, 512, true, false, 0, true>), dim3(1, nb),
-                           dim3(1024), 0, st, M, stride, sc, sh, resid, Y, V8, ev, stag, cus);
-    else if (form == 0 && r3)
+    if constexpr (WRITE_Y) {  // Y / residual non-temporal at large batches (YNT)
+        if (r3 && nb >= 1024) {
+            hipLaunchKernelGGL((kv::wino88i32_out_kernel<RESID, true, 512, true, false, true>), dim3(1, nb),
+                               dim3(1024), 0, st, M, stride, sc, sh, resid, Y, V8, ev);
+            KV_HIP(hipGetLastError());
+            return KV_OK;
+        }
+    }
+    if (r3)
         hipLaunchKernelGGL((kv::wino88i32_out_kernel<RESID, WRITE_Y, 512, true>), dim3(1, nb), dim3(1024), 0, st, M,
-                           stride, sc, sh, resid, Y, V8, ev, stag, cus);
-    else if (form == 0)
-        hipLaunchKernelGGL((kv::wino88i32_out_kernel<RESID, WRITE_Y, 512>), dim3(1, nb), dim3(1024), 0, st, M, stride,
-                           sc, sh, resid, Y, V8, ev, stag, cus);
-    else if (r3)
-        hipLaunchKernelGGL((kv::wino88i32_out2_kernel<RESID, WRITE_Y, true>), dim3(1, nb), dim3(1024), 0, st, M,
-                           stride, sc, sh, resid, Y, V8, ev, stag, 2 * cus);
+                           stride, sc, sh, resid, Y, V8, ev);
     else
-        hipLaunchKernelGGL((kv::wino88i32_out2_kernel<RESID, WRITE_Y>), dim3(1, nb), dim3(1024), 0, st, M, stride,
-                           sc, sh, resid, Y, V8, ev, stag, 2 * cus);
+        hipLaunchKernelGGL((kv::wino88i32_out_kernel<RESID, WRITE_Y, 512>), dim3(1, nb), dim3(1024), 0, st, M, stride,
+                           sc, sh, resid, Y, V8, ev);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
@@ -1468,17 +1280,15 @@ static int launch_wino88i32v_out(kv_net* net, int l, const float* M, int nb, int
                                  float* Y, int8_t* V8, int* ev, hipStream_t st) {
     const float* W = net->w;
     hipLaunchKernelGGL((kv::wino88i32v_out_kernel<RESID, WRITE_Y>), dim3(1, nb), dim3(1024), 0, st, M, stride,
-                       W + net->off.scale[l], W + net->off.shift[l], resid, Y, V8, ev, out_stag(), device_cus());
+                       W + net->off.scale[l], W + net->off.shift[l], resid, Y, V8, ev);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
 
-// the fp32 tower's int8-digit GEMM of one conv (K 256: one segment, per-row exponents)
+// the fp32 tower's int8-digit GEMM of one conv
 template <int K>
 static int i8f32_gemm(const int8_t* V8, const int* ev, const int8_t* U8, const int* eu, float* M, int rows, int stride,
-                      bool seg, hipStream_t st, bool r3 = false, int share = 1) {
-    constexpr int D = kv::kI8DigitsF32;
-    const I8f32Form& f = i8f32_form();
+                      hipStream_t st, bool r3 = false, int share = 1) {
     if (r3) {  // KV_PATH_WINO88_I8F32R3 (96-byte row lines): the 64-k-stage kernel, tile count as the 4-digit one's
         // (round 6: 357 vs 375 us for the 32-k form on 128-byte lines, forward -3-5 %, profiles/r06_saddr_ab.log)
         const int tpw = i8f32_tiles_per_wg(rows, share);
@@ -1493,19 +1303,6 @@ static int i8f32_gemm(const int8_t* V8, const int* ev, const int8_t* U8, const i
         note_dom<K>("wino88i32_gemm_r3k64_kernel<512,1>");
         return launch_wino88i32_gemm_r3k64<K, 1>(V8, ev, U8, eu, M, rows, stride, st);
     }
-    if constexpr (K == 512)
-        if (seg) {
-            note_dom<K>("wino88i32_gemm_kernel<512,32,3,2>");
-            return launch_wino88i32_gemm<K, 32, 3, 2>(V8, ev, U8, eu, M, rows, stride, true, st);
-        }
-    if (f.r4) {
-        note_dom<K>("wino88i_gemm_kernel<512,4>");
-        return launch_wino88i_gemm<K, D>(V8, ev, U8, eu, M, rows, stride, st);
-    }
-    if (f.persist) {
-        note_dom<K>("wino88i32_gemm_kernel<512,32,3,1>");
-        return launch_wino88i32_gemm<K, 32, 3, 1>(V8, ev, U8, eu, M, rows, stride, true, st);
-    }
     const int tpw = i8f32_tiles_per_wg(rows);
     if (tpw == 5) {
         note_dom<K>("wino88i32_gemm_lagt_kernel<512,5>");
@@ -1516,43 +1313,39 @@ static int i8f32_gemm(const int8_t* V8, const int* ev, const int8_t* U8, const i
         return launch_wino88i32_gemm_lagt<K, 4>(V8, ev, U8, eu, M, rows, stride, st);
     }
     note_dom<K>("wino88i32_gemm_lag_kernel<512,false>");
-    return launch_wino88i32_gemm_lag<K, false>(V8, ev, U8, eu, M, rows, stride, st);
+    return launch_wino88i32_gemm_lag<K>(V8, ev, U8, eu, M, rows, stride, st);
 }
 
-// conv l's GEMM; slice: V (fp32; v64: conv2's fp64 V256) -> digits first. (mark: the engine's timing hook
+// conv l's GEMM; slice (conv2 only): V256 (fp32; v64: fp64) -> digits first. (mark: the engine's timing hook
 // brackets the slice, when there is one, and the GEMM)
 // r3 (KV_PATH_WINO88_I8F32R3): 3 radix-256 digits -- conv2's slice, the weights' digits and the 6-pair GEMM
 static int wino88i32_gemm_layer(kv_net* net, int l, int K, int rows, int stride, bool slice, bool mark, bool v64,
                                 hipStream_t st, bool r3 = false) {
     constexpr int D = kv::kI8DigitsF32;
-    const bool seg = K == 512 && i8f32_form().seg && !v64 && !r3;
     float* M = (float*)net->Mw;
     int rc;
     if (mark && net->res_a) KV_HIP(hipEventRecord(net->res_a, st));
+    KV_REQUIRE(!slice || K == 256, KV_EINVAL, "wino88i32: the output kernels write the digits of K 512");
     if (slice && r3) {
-        KV_REQUIRE(K == 256, KV_EINVAL, "wino88i32r3: the output kernels write the digits of K 512");
-        if ((rc = launch_wino88i_slice<256, D, float, 1, false, true>((const float*)net->V256, rows, stride,
+        if ((rc = launch_wino88i_slice<256, D, float, false, true>((const float*)net->V256, rows, stride,
                                                                       kv::W88_XI, net->V8, net->ev8, st)))
             return rc;
     } else if (slice && v64) {
-        KV_REQUIRE(K == 256, KV_EINVAL, "wino88i32v: the output kernels write the digits of K 512");
         if ((rc = launch_wino88i_slice<256, D>((const double*)net->V256, rows, stride, kv::W88_XI, net->V8, net->ev8,
                                                st)))
             return rc;
     } else if (slice) {
-        const float* Vsrc = K == 256 ? (const float*)net->V256 : (const float*)net->V;
-        rc = K == 256 ? launch_wino88i_slice<256, D>(Vsrc, rows, stride, kv::W88_XI, net->V8, net->ev8, st)
-             : seg    ? launch_wino88i_slice<512, D, float, 2>(Vsrc, rows, stride, kv::W88_XI, net->V8, net->ev8, st)
-                      : launch_wino88i_slice<512, D>(Vsrc, rows, stride, kv::W88_XI, net->V8, net->ev8, st);
-        if (rc) return rc;
+        if ((rc = launch_wino88i_slice<256, D>((const float*)net->V256, rows, stride, kv::W88_XI, net->V8, net->ev8,
+                                               st)))
+            return rc;
     }
     const int8_t* U = (r3 ? net->U88r3 : net->U88i32) + net->uoff88[l] * D;
     const int* eu = (r3 ? net->eu88r3 : net->eu88i32) + net->euoff[l];
     // beside a leader (kv_net::leader): this GEMM starts once the leader's GEMM of the same conv is done, so it
     // runs under the leader's output kernel instead of under its GEMM
     if (net->leader && net->leader->gemm_done[l]) KV_HIP(hipStreamWaitEvent(st, net->leader->gemm_done[l], 0));
-    rc = K == 256 ? i8f32_gemm<256>(net->V8, net->ev8, U, eu, M, rows, stride, false, st, r3, net->cu_share)
-                  : i8f32_gemm<512>(net->V8, net->ev8, U, eu, M, rows, stride, seg, st, r3, net->cu_share);
+    rc = K == 256 ? i8f32_gemm<256>(net->V8, net->ev8, U, eu, M, rows, stride, st, r3, net->cu_share)
+                  : i8f32_gemm<512>(net->V8, net->ev8, U, eu, M, rows, stride, st, r3, net->cu_share);
     if (rc) return rc;
     if (net->gemm_done[l]) KV_HIP(hipEventRecord(net->gemm_done[l], st));
     if (mark && net->res_b) KV_HIP(hipEventRecord(net->res_b, st));
@@ -1597,33 +1390,29 @@ struct HeadsOut {
 };
 
 // v64 (KV_PATH_WINO88_I8F32V): conv2's V256 is fp64 (the stem's / wino88d_in_kernel's) and every output
-// kernel is wino88i32v_out_kernel (the slice and segment forms do not apply)
+// kernel is wino88i32v_out_kernel
 // ho: the last block's output transform runs the heads too (net->pfeat, ho->value) and writes no X
 // v8_ready: conv2's digits and exponents are in V8 / ev8 already (stem_r3_kernel): no slice pass over V256
 static int wino88i32_blocks(kv_net* net, int nb, bool mark, bool v64, hipStream_t st, bool r3 = false,
                             const HeadsOut* ho = nullptr, bool v8_ready = false) {
     const int rows = nb, stride = rows;
-    float* V = (float*)net->V;
     const float* M = (const float*)net->Mw;
-    const bool sf = i8f32_form().slice && !v64 && !r3, seg = i8f32_form().seg && !v64 && !r3;
     int8_t* V8 = net->V8;
     int* ev = net->ev8;
     int rc;
     if ((rc = wino88i32_gemm_layer(net, 1, 256, rows, stride, !v8_ready, false, v64, st, r3))) return rc;
-    rc = v64  ? launch_wino88i32v_out<false, true>(net, 1, M, nb, stride, nullptr, net->X, V8, ev, st)
-         : sf ? launch_wino88_out<false, true, true>(net, 1, M, nb, stride, nullptr, net->X, V, st)
-              : launch_wino88i32_out<false, true>(net, 1, M, nb, stride, nullptr, net->X, V8, ev, seg, st, r3);
+    rc = v64 ? launch_wino88i32v_out<false, true>(net, 1, M, nb, stride, nullptr, net->X, V8, ev, st)
+             : launch_wino88i32_out<false, true>(net, 1, M, nb, stride, nullptr, net->X, V8, ev, st, r3);
     if (rc) return rc;
     if (mark && net->timing) KV_HIP(hipEventRecord(net->ev[1], st));
     for (int r = 0; r < 5; ++r) {
         const int l1 = 2 + 2 * r, l2 = 3 + 2 * r;
         const bool m = mark && r == 2;
-        if ((rc = wino88i32_gemm_layer(net, l1, 512, rows, stride, sf, m, v64, st, r3))) return rc;
-        rc = v64  ? launch_wino88i32v_out<false, false>(net, l1, M, nb, stride, nullptr, nullptr, V8, ev, st)
-             : sf ? launch_wino88_out<false, false, true>(net, l1, M, nb, stride, nullptr, nullptr, V, st)
-                  : launch_wino88i32_out<false, false>(net, l1, M, nb, stride, nullptr, nullptr, V8, ev, seg, st, r3);
+        if ((rc = wino88i32_gemm_layer(net, l1, 512, rows, stride, false, m, v64, st, r3))) return rc;
+        rc = v64 ? launch_wino88i32v_out<false, false>(net, l1, M, nb, stride, nullptr, nullptr, V8, ev, st)
+                 : launch_wino88i32_out<false, false>(net, l1, M, nb, stride, nullptr, nullptr, V8, ev, st, r3);
         if (rc) return rc;
-        if ((rc = wino88i32_gemm_layer(net, l2, 512, rows, stride, sf, false, v64, st, r3))) return rc;
+        if ((rc = wino88i32_gemm_layer(net, l2, 512, rows, stride, false, false, v64, st, r3))) return rc;
         if (r == 4 && ho) {
             const float* W = net->w;
             const kv::PackOffsets& o = net->off;
@@ -1633,9 +1422,8 @@ static int wino88i32_blocks(kv_net* net, int nb, bool mark, bool v64, hipStream_
         } else if (r == 4)
             rc = launch_wino88_out<true, true, false>(net, l2, M, nb, stride, net->X, net->X, nullptr, st);
         else
-            rc = v64  ? launch_wino88i32v_out<true, true>(net, l2, M, nb, stride, net->X, net->X, V8, ev, st)
-                 : sf ? launch_wino88_out<true, true, true>(net, l2, M, nb, stride, net->X, net->X, V, st)
-                      : launch_wino88i32_out<true, true>(net, l2, M, nb, stride, net->X, net->X, V8, ev, seg, st, r3);
+            rc = v64 ? launch_wino88i32v_out<true, true>(net, l2, M, nb, stride, net->X, net->X, V8, ev, st)
+                     : launch_wino88i32_out<true, true>(net, l2, M, nb, stride, net->X, net->X, V8, ev, st, r3);
         if (rc) return rc;
     }
     if (mark && net->timing) KV_HIP(hipEventRecord(net->ev[2], st));
@@ -1656,9 +1444,7 @@ static WsNeed ws_need(int path) {
         case KV_PATH_WINO88_F64: return {{P88 * 512 * d, P88 * 512 * d, P88 * 256 * d, 0}};
         case KV_PATH_WINO88_I8: return {{0, P88 * 512 * d, P88 * 256 * d, P88 * 512 * kv::kI8Digits}};
         case KV_PATH_WINO88_I8R: return {{0, P88 * 512 * d, P88 * 256 * d, P88 * 512 * 4}};
-        case KV_PATH_WINO88_I8F32:
-            return {{i8f32_form().slice ? P88 * 512 * f : 0, P88 * 512 * f, P88 * 256 * f,
-                     P88 * 512 * kv::kI8DigitsF32}};
+        case KV_PATH_WINO88_I8F32: return {{0, P88 * 512 * f, P88 * 256 * f, P88 * 512 * kv::kI8DigitsF32}};
         case KV_PATH_WINO88_I8F32V: return {{0, P88 * 512 * f, P88 * 256 * d, P88 * 512 * kv::kI8DigitsF32}};
         case KV_PATH_WINO88_I8F32R3: return {{0, P88 * 512 * f, P88 * 256 * f, P88 * 512 * kv::kI8DigitsF32}};
         default: return {{0, 0, 0, 0}};  // direct: the split-K slab only
@@ -1906,12 +1692,12 @@ static int ensure_path(kv_net* net, int path) {
                     rc = ci == 256 ? launch_wino88i_slice<256, kv::kI8DigitsF32>(U64, co, co, kv::W88_XI, dst, ex, 0)
                                    : launch_wino88i_slice<512, kv::kI8DigitsF32>(U64, co, co, kv::W88_XI, dst, ex, 0);
                 else if (r8)
-                    rc = ci == 256 ? launch_wino88i_slice<256, 4, double, 1, true>(U64, co, co, kv::W88_XI, dst, ex, 0)
-                                   : launch_wino88i_slice<512, 4, double, 1, true>(U64, co, co, kv::W88_XI, dst, ex, 0);
+                    rc = ci == 256 ? launch_wino88i_slice<256, 4, double, true>(U64, co, co, kv::W88_XI, dst, ex, 0)
+                                   : launch_wino88i_slice<512, 4, double, true>(U64, co, co, kv::W88_XI, dst, ex, 0);
                 else if (r3)
                     rc = ci == 256
-                             ? launch_wino88i_slice<256, 4, double, 1, false, true>(U64, co, co, kv::W88_XI, dst, ex, 0)
-                             : launch_wino88i_slice<512, 4, double, 1, false, true>(U64, co, co, kv::W88_XI, dst, ex, 0);
+                             ? launch_wino88i_slice<256, 4, double, false, true>(U64, co, co, kv::W88_XI, dst, ex, 0)
+                             : launch_wino88i_slice<512, 4, double, false, true>(U64, co, co, kv::W88_XI, dst, ex, 0);
                 else
                     rc = ci == 256 ? launch_wino88i_slice<256>(U64, co, co, kv::W88_XI, dst, ex, 0)
                                    : launch_wino88i_slice<512>(U64, co, co, kv::W88_XI, dst, ex, 0);
@@ -2152,12 +1938,7 @@ static int net_calibrate(kv_net* net) {
 static int net_prepare(kv_net* net) {
     if (!net->loaded) return KV_OK;
     KV_HIP(hipSetDevice(net->device));
-    if (net->precision == KV_PREC_FP32 && net->algo == KV_ALGO_AUTO) {
-        const char* e = getenv("KV_CALIBRATE");  // "0": skip, AUTO keeps F(8x8) / direct (timing probes only)
-        if (!(e && e[0] == '0')) return net_calibrate(net);
-        net->auto_large = KV_PATH_WINO88;
-        net->auto_small = KV_PATH_DIRECT;
-    }
+    if (net->precision == KV_PREC_FP32 && net->algo == KV_ALGO_AUTO) return net_calibrate(net);
     // no calibration for this setting: kv_net_calibration must not report an earlier one's errors
     net->calib = kv_calib{};
     int rc;
@@ -2309,15 +2090,12 @@ int kv_net_forward_boards_legal(kv_net* net, const int8_t* boards_dev, int B, co
 int kv_dev_wino88i(int device, const double* V, int rows, const double* U, int K, int digits, int seg, double* M,
                    int8_t* v_digits, int* v_exp) {
     KV_REQUIRE(V && U && M && rows > 0 && rows % 128 == 0 && rows <= kMaxBoards && (K == 256 || K == 512) &&
-                   (digits == 4 || digits == 5) &&
-                   (!seg || (seg == 1 && digits == 4 && K == 512) || (seg == 2 && digits == 4) ||
-                    (seg == 3 && digits == 4)),
+                   (digits == 4 || digits == 5) && (!seg || ((seg == 2 || seg == 3) && digits == 4)),
                KV_EINVAL, "kv_dev_wino88i: bad arguments (rows %d must be a multiple of 128, K %d 256 or 512, "
-               "digits %d 4 or 5, seg %d: 1 only with 4 digits and K 512, 2 (radix 256) and 3 (3 radix-256 "
-               "digits in 96-byte row lines) only with 4 digits)",
+               "digits %d 4 or 5, seg %d: 0, or with 4 digits 2 (radix 256) or 3 (3 radix-256 digits in 96-byte "
+               "row lines))",
                rows, K, digits, seg);
     const bool r8 = seg == 2, r3 = seg == 3;
-    const int nseg = seg == 1 ? 2 : 1;
     KV_HIP(hipSetDevice(device));
     const size_t nv = (size_t)kv::W88_XI * rows * K, nu = (size_t)kv::W88_XI * 512 * K;
     const size_t nm = (size_t)kv::W88_XI * rows * 512;
@@ -2332,51 +2110,50 @@ int kv_dev_wino88i(int device, const double* V, int rows, const double* U, int K
     KV_HIP(v8.alloc(nv * digits));
     KV_HIP(hipMemset(v8.p, 0, nv * digits));  // R3 lines fill 3/4 of it
     KV_HIP(u8.alloc(nu * digits));
-    KV_HIP(ev.alloc((size_t)kv::W88_XI * rows * nseg));
+    KV_HIP(ev.alloc((size_t)kv::W88_XI * rows));
     KV_HIP(eu.alloc((size_t)kv::W88_XI * 512));
     KV_HIP(hipMemcpy(dv.p, V, nv * sizeof(double), hipMemcpyHostToDevice));
     KV_HIP(hipMemcpy(du.p, U, nu * sizeof(double), hipMemcpyHostToDevice));
     int rc;
     if (r8) {  // KV_PATH_WINO88_I8R: 4 radix-256 digit planes, 13 pairs, fp64 M
-        rc = K == 256 ? launch_wino88i_slice<256, 4, double, 1, true>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0)
-                      : launch_wino88i_slice<512, 4, double, 1, true>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0);
+        rc = K == 256 ? launch_wino88i_slice<256, 4, double, true>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0)
+                      : launch_wino88i_slice<512, 4, double, true>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0);
         if (!rc)
-            rc = K == 256 ? launch_wino88i_slice<256, 4, double, 1, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0)
-                          : launch_wino88i_slice<512, 4, double, 1, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
+            rc = K == 256 ? launch_wino88i_slice<256, 4, double, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0)
+                          : launch_wino88i_slice<512, 4, double, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
         if (!rc)
             rc = K == 256 ? i8r_gemm<256>(v8.p, ev.p, u8.p, eu.p, dm.p, rows, rows, 0)
                           : i8r_gemm<512>(v8.p, ev.p, u8.p, eu.p, dm.p, rows, rows, 0);
-    } else if (digits == 5) {  // the fp64 domain: fp64 M
+    } else if (digits == 5) {  // the fp64 domain (KV_PREC_I8X5's GEMM): fp64 M
         rc = K == 256 ? launch_wino88i_slice<256>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0)
                       : launch_wino88i_slice<512>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0);
         if (!rc)
             rc = K == 256 ? launch_wino88i_slice<256>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0)
                           : launch_wino88i_slice<512>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
         if (!rc)
-            rc = K == 256 ? launch_wino88i_gemm<256>(v8.p, ev.p, u8.p, eu.p, dm.p, rows, rows, 0)
-                          : launch_wino88i_gemm<512>(v8.p, ev.p, u8.p, eu.p, dm.p, rows, rows, 0);
+            rc = K == 256 ? i8x5_gemm<256>(v8.p, ev.p, u8.p, eu.p, dm.p, rows, rows, 0)
+                          : i8x5_gemm<512>(v8.p, ev.p, u8.p, eu.p, dm.p, rows, rows, 0);
     } else if (r3) {  // KV_PATH_WINO88_I8F32R3: 3 radix-256 digits in row lines, 6 pairs, M rounded to fp32
         constexpr int D = kv::kI8DigitsF32;
-        rc = K == 256 ? launch_wino88i_slice<256, D, double, 1, false, true>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0)
-                      : launch_wino88i_slice<512, D, double, 1, false, true>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0);
+        rc = K == 256 ? launch_wino88i_slice<256, D, double, false, true>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0)
+                      : launch_wino88i_slice<512, D, double, false, true>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0);
         if (!rc)
             rc = K == 256
-                     ? launch_wino88i_slice<256, D, double, 1, false, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0)
-                     : launch_wino88i_slice<512, D, double, 1, false, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
+                     ? launch_wino88i_slice<256, D, double, false, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0)
+                     : launch_wino88i_slice<512, D, double, false, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
         if (!rc)
-            rc = K == 256 ? i8f32_gemm<256>(v8.p, ev.p, u8.p, eu.p, dmf.p, rows, rows, false, 0, true)
-                          : i8f32_gemm<512>(v8.p, ev.p, u8.p, eu.p, dmf.p, rows, rows, false, 0, true);
+            rc = K == 256 ? i8f32_gemm<256>(v8.p, ev.p, u8.p, eu.p, dmf.p, rows, rows, 0, true)
+                          : i8f32_gemm<512>(v8.p, ev.p, u8.p, eu.p, dmf.p, rows, rows, 0, true);
     } else {  // the fp32 domain: 4 digits, M rounded to fp32 (returned widened)
         constexpr int D = kv::kI8DigitsF32;
         rc = K == 256 ? launch_wino88i_slice<256, D>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0)
                       : launch_wino88i_slice<512, D>(du.p, 512, 512, kv::W88_XI, u8.p, eu.p, 0);
         if (!rc)
             rc = K == 256 ? launch_wino88i_slice<256, D>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0)
-                 : seg    ? launch_wino88i_slice<512, D, double, 2>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0)
                           : launch_wino88i_slice<512, D>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
-        if (!rc)  // the product's GEMM for this exponent form (i8f32_gemm)
-            rc = K == 256 ? i8f32_gemm<256>(v8.p, ev.p, u8.p, eu.p, dmf.p, rows, rows, false, 0)
-                          : i8f32_gemm<512>(v8.p, ev.p, u8.p, eu.p, dmf.p, rows, rows, seg != 0, 0);
+        if (!rc)  // the product's GEMM (i8f32_gemm)
+            rc = K == 256 ? i8f32_gemm<256>(v8.p, ev.p, u8.p, eu.p, dmf.p, rows, rows, 0)
+                          : i8f32_gemm<512>(v8.p, ev.p, u8.p, eu.p, dmf.p, rows, rows, 0);
     }
     if (rc) return rc;
     KV_HIP(hipDeviceSynchronize());
@@ -2388,7 +2165,7 @@ int kv_dev_wino88i(int device, const double* V, int rows, const double* U, int K
         for (size_t i = 0; i < nm; ++i) M[i] = mf[i];
     }
     if (v_digits) KV_HIP(hipMemcpy(v_digits, v8.p, nv * digits, hipMemcpyDeviceToHost));
-    if (v_exp) KV_HIP(hipMemcpy(v_exp, ev.p, (size_t)kv::W88_XI * rows * nseg * sizeof(int), hipMemcpyDeviceToHost));
+    if (v_exp) KV_HIP(hipMemcpy(v_exp, ev.p, (size_t)kv::W88_XI * rows * sizeof(int), hipMemcpyDeviceToHost));
     return KV_OK;
 }
 
@@ -2444,11 +2221,11 @@ int kv_dev_wino88i_r3(int device, const double* V, int rows, const double* U, in
     KV_HIP(hipMemsetD32((hipDeviceptr_t)dm.p, (int)kDevMFill, nms));
     KV_HIP(hipMemcpy(dv.p, V, nv * sizeof(double), hipMemcpyHostToDevice));
     KV_HIP(hipMemcpy(du.p, U, nu * sizeof(double), hipMemcpyHostToDevice));
-    int rc = K == 256 ? launch_wino88i_slice<256, D, double, 1, false, true>(du.p, 512, 512, X, u8.p, eu.p, 0)
-                      : launch_wino88i_slice<512, D, double, 1, false, true>(du.p, 512, 512, X, u8.p, eu.p, 0);
+    int rc = K == 256 ? launch_wino88i_slice<256, D, double, false, true>(du.p, 512, 512, X, u8.p, eu.p, 0)
+                      : launch_wino88i_slice<512, D, double, false, true>(du.p, 512, 512, X, u8.p, eu.p, 0);
     if (!rc)
-        rc = K == 256 ? launch_wino88i_slice<256, D, double, 1, false, true>(dv.p, rows, rows, X, v8c.p, evc.p, 0)
-                      : launch_wino88i_slice<512, D, double, 1, false, true>(dv.p, rows, rows, X, v8c.p, evc.p, 0);
+        rc = K == 256 ? launch_wino88i_slice<256, D, double, false, true>(dv.p, rows, rows, X, v8c.p, evc.p, 0)
+                      : launch_wino88i_slice<512, D, double, false, true>(dv.p, rows, rows, X, v8c.p, evc.p, 0);
     if (rc) return rc;
     // the compact lines and exponents into rows [row0, row0 + rows) of the strided buffers
     KV_HIP(hipMemcpy2D(v8s.p + (size_t)row0 * line, (size_t)stride * line, v8c.p, (size_t)rows * line,
@@ -2461,7 +2238,7 @@ int kv_dev_wino88i_r3(int device, const double* V, int rows, const double* U, in
     auto gemm = [&](auto kc) -> int {
         constexpr int KK = decltype(kc)::value;
         switch (tpw) {
-            case 0: return i8f32_gemm<KK>(v8, ev, u8.p, eu.p, m, rows, stride, false, 0, true);
+            case 0: return i8f32_gemm<KK>(v8, ev, u8.p, eu.p, m, rows, stride, 0, true);
             case 1: return launch_wino88i32_gemm_r3k64<KK, 1>(v8, ev, u8.p, eu.p, m, rows, stride, 0, 1, nwg);
             case 4: return launch_wino88i32_gemm_r3k64<KK, 4>(v8, ev, u8.p, eu.p, m, rows, stride, 0, 1, nwg);
             default: return launch_wino88i32_gemm_r3k64<KK, 5>(v8, ev, u8.p, eu.p, m, rows, stride, 0, 1, nwg);
@@ -2486,19 +2263,13 @@ int kv_dev_wino88i_r3(int device, const double* V, int rows, const double* U, in
 
 }  // extern "C"
 
-// the per-row fused output kernel of kv_dev_wino88i32_out: the held-V form (hold) or the product's default
+// the per-row fused output kernel of kv_dev_wino88i32_out
 template <bool RESID, bool R3>
-static void dev_out_rowform(int form, const float* M, int rows, const float* sc, const float* sh, float* y,
-                            int8_t* v8, int* ev) {
+static void dev_out_rowform(const float* M, int rows, const float* sc, const float* sh, float* y, int8_t* v8,
+                            int* ev) {
     const float* rs = RESID ? y : nullptr;  // Y doubles as the residual (in place, as the tower runs it)
-    if (form == 2)
-        (void)launch_wino88i32_outp<RESID, true>(M, rows, rows, sc, sh, rs, y, v8, ev, 0, R3);
-    else if (form == 0)
-        hipLaunchKernelGGL((kv::wino88i32_out_kernel<RESID, true, 512, R3>), dim3(1, rows), dim3(1024), 0, 0, M, rows,
-                           sc, sh, rs, y, v8, ev, 0, 0);
-    else
-        hipLaunchKernelGGL((kv::wino88i32_out2_kernel<RESID, true, R3>), dim3(1, rows), dim3(1024), 0, 0, M, rows, sc,
-                           sh, rs, y, v8, ev, 0, 0);
+    hipLaunchKernelGGL((kv::wino88i32_out_kernel<RESID, true, 512, R3>), dim3(1, rows), dim3(1024), 0, 0, M, rows, sc,
+                       sh, rs, y, v8, ev);
 }
 
 extern "C" {
@@ -2508,6 +2279,9 @@ int kv_dev_wino88i32_out(int device, const float* M, int rows, const float* scal
     KV_REQUIRE(M && scale && shift && Y && v_digits && v_exp && rows > 0 && rows % 128 == 0 && rows <= kMaxBoards,
                KV_EINVAL, "kv_dev_wino88i32_out: bad arguments (rows %d: a multiple of 128, at most %d)", rows,
                kMaxBoards);
+    const bool v64 = (fused & 4) != 0, r3 = (fused & 16) != 0;
+    KV_REQUIRE(!(fused & ~(1 | 4 | 16)), KV_EINVAL, "kv_dev_wino88i32_out: fused %d (bits 0, 2 and 4 only)", fused);
+    KV_REQUIRE(!(r3 && v64), KV_EINVAL, "kv_dev_wino88i32_out: bit 4 (3 radix-256 digits) has fp32 V only");
     KV_HIP(hipSetDevice(device));
     const size_t nm = (size_t)kv::W88_XI * rows * 512, ny = (size_t)rows * 64 * 512;
     kv::DevBuf<float> dm, dsc, dsh, dy, dv;
@@ -2520,18 +2294,7 @@ int kv_dev_wino88i32_out(int device, const float* M, int rows, const float* scal
     KV_HIP(dv.alloc(nm));
     KV_HIP(v8.alloc(nm * kv::kI8DigitsF32));
     KV_HIP(hipMemset(v8.p, 0, nm * kv::kI8DigitsF32));  // R3 lines fill 3/4 of it
-    // the per-row fused form: bit 3 the 64-register kernel, bit 5 the persistent one, neither the product's
-    // default (KV_I8F32_OUT)
-    const bool seg = (fused & 2) != 0, v64 = (fused & 4) != 0, r64 = (fused & 8) != 0, r3 = (fused & 16) != 0;
-    const bool pers = (fused & 32) != 0;
-    const int form = pers ? 2 : r64 ? 1 : i8f32_form().out;
-    KV_REQUIRE(!(seg && v64), KV_EINVAL, "kv_dev_wino88i32_out: fp64 V (bit 2) has per-row exponents only");
-    KV_REQUIRE(!r3 || (!seg && !v64), KV_EINVAL, "kv_dev_wino88i32_out: bit 4 (3 radix-256 digits) has per-row "
-               "fp32 V only");
-    KV_REQUIRE(!(r64 || pers) || ((fused & 1) && !seg && !v64 && !(r64 && pers)), KV_EINVAL,
-               "kv_dev_wino88i32_out: bits 3 / 5 (the 64-register / persistent form) are forms of the fused per-row "
-               "kernel");
-    KV_HIP(ev.alloc((size_t)kv::W88_XI * rows * 2));
+    KV_HIP(ev.alloc((size_t)kv::W88_XI * rows));
     KV_HIP(hipMemcpy(dm.p, M, nm * sizeof(float), hipMemcpyHostToDevice));
     KV_HIP(hipMemcpy(dsc.p, scale, 512 * sizeof(float), hipMemcpyHostToDevice));
     KV_HIP(hipMemcpy(dsh.p, shift, 512 * sizeof(float), hipMemcpyHostToDevice));
@@ -2545,10 +2308,10 @@ int kv_dev_wino88i32_out(int device, const float* M, int rows, const float* scal
     if (v64 && (fused & 1)) {
         if (resid)
             hipLaunchKernelGGL((kv::wino88i32v_out_kernel<true, true>), dim3(1, rows), dim3(1024), 0, 0, dm.p, rows, sc,
-                               sh, dy.p, dy.p, v8.p, ev.p, 0, 0);
+                               sh, dy.p, dy.p, v8.p, ev.p);
         else
             hipLaunchKernelGGL((kv::wino88i32v_out_kernel<false, true>), dim3(1, rows), dim3(1024), 0, 0, dm.p, rows,
-                               sc, sh, nullptr, dy.p, v8.p, ev.p, 0, 0);
+                               sc, sh, nullptr, dy.p, v8.p, ev.p);
         KV_HIP(hipGetLastError());
     } else if (v64) {  // Y, then fp64 V from Y, then its digits
         if (resid)
@@ -2565,19 +2328,12 @@ int kv_dev_wino88i32_out(int device, const float* M, int rows, const float* scal
         if (rc) return rc;
         KV_HIP(hipDeviceSynchronize());
     } else if (fused & 1) {
-        if (seg) {
-            if (resid)
-                hipLaunchKernelGGL((kv::wino88i32_out_kernel<true, true, 256>), dim3(2, rows), dim3(512), 0, 0, dm.p,
-                                   rows, sc, sh, dy.p, dy.p, v8.p, ev.p, 0, 0);
-            else
-                hipLaunchKernelGGL((kv::wino88i32_out_kernel<false, true, 256>), dim3(2, rows), dim3(512), 0, 0, dm.p,
-                                   rows, sc, sh, nullptr, dy.p, v8.p, ev.p, 0, 0);
-        } else if (resid) {
-            if (r3) dev_out_rowform<true, true>(form, dm.p, rows, sc, sh, dy.p, v8.p, ev.p);
-            else dev_out_rowform<true, false>(form, dm.p, rows, sc, sh, dy.p, v8.p, ev.p);
+        if (resid) {
+            if (r3) dev_out_rowform<true, true>(dm.p, rows, sc, sh, dy.p, v8.p, ev.p);
+            else dev_out_rowform<true, false>(dm.p, rows, sc, sh, dy.p, v8.p, ev.p);
         } else {
-            if (r3) dev_out_rowform<false, true>(form, dm.p, rows, sc, sh, dy.p, v8.p, ev.p);
-            else dev_out_rowform<false, false>(form, dm.p, rows, sc, sh, dy.p, v8.p, ev.p);
+            if (r3) dev_out_rowform<false, true>(dm.p, rows, sc, sh, dy.p, v8.p, ev.p);
+            else dev_out_rowform<false, false>(dm.p, rows, sc, sh, dy.p, v8.p, ev.p);
         }
         KV_HIP(hipGetLastError());
     } else {
@@ -2588,16 +2344,15 @@ int kv_dev_wino88i32_out(int device, const float* M, int rows, const float* scal
             hipLaunchKernelGGL((kv::wino88_out_kernel<false, true, true>), dim3(512 / 256, rows), dim3(256), 0, 0,
                                dm.p, rows, sc, sh, nullptr, dy.p, dv.p);
         KV_HIP(hipGetLastError());
-        int rc = seg  ? launch_wino88i_slice<512, kv::kI8DigitsF32, float, 2>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0)
-                 : r3 ? launch_wino88i_slice<512, kv::kI8DigitsF32, float, 1, false, true>(dv.p, rows, rows, kv::W88_XI,
-                                                                                           v8.p, ev.p, 0)
-                      : launch_wino88i_slice<512, kv::kI8DigitsF32>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
+        int rc = r3 ? launch_wino88i_slice<512, kv::kI8DigitsF32, float, false, true>(dv.p, rows, rows, kv::W88_XI,
+                                                                                          v8.p, ev.p, 0)
+                    : launch_wino88i_slice<512, kv::kI8DigitsF32>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
         if (rc) return rc;
     }
     KV_HIP(hipDeviceSynchronize());
     KV_HIP(hipMemcpy(Y, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost));
     KV_HIP(hipMemcpy(v_digits, v8.p, nm * kv::kI8DigitsF32, hipMemcpyDeviceToHost));
-    KV_HIP(hipMemcpy(v_exp, ev.p, (size_t)kv::W88_XI * rows * (seg ? 2 : 1) * sizeof(int), hipMemcpyDeviceToHost));
+    KV_HIP(hipMemcpy(v_exp, ev.p, (size_t)kv::W88_XI * rows * sizeof(int), hipMemcpyDeviceToHost));
     return KV_OK;
 }
 
@@ -2631,7 +2386,7 @@ int kv_dev_tower_front(int device, const int8_t* boards, int nb, int rows, const
         hipLaunchKernelGGL(kv::stem_kernel<4>, dim3(4, rows / 2), dim3(256), 0, 0, db.p, nb, dw.p, dsc.p, dsh.p, dv.p,
                            rows, nullptr);
         KV_HIP(hipGetLastError());
-        const int rc = launch_wino88i_slice<256, kv::kI8DigitsF32, float, 1, false, true>(dv.p, rows, rows, kv::W88_XI,
+        const int rc = launch_wino88i_slice<256, kv::kI8DigitsF32, float, false, true>(dv.p, rows, rows, kv::W88_XI,
                                                                                           v8.p, ev.p, 0);
         if (rc) return rc;
     }
@@ -2714,10 +2469,10 @@ int kv_dev_wino88r_out(int device, const double* M, int rows, const float* scale
     if (fused) {
         if (resid)
             hipLaunchKernelGGL((kv::wino88i64r_out_kernel<true, true>), dim3(1, rows), dim3(1024), 0, 0, dm.p, rows,
-                               dsc.p, dsh.p, rs, dy.p, v8.p, ev.p, 0, 0);
+                               dsc.p, dsh.p, rs, dy.p, v8.p, ev.p);
         else
             hipLaunchKernelGGL((kv::wino88i64r_out_kernel<false, true>), dim3(1, rows), dim3(1024), 0, 0, dm.p, rows,
-                               dsc.p, dsh.p, rs, dy.p, v8.p, ev.p, 0, 0);
+                               dsc.p, dsh.p, rs, dy.p, v8.p, ev.p);
         KV_HIP(hipGetLastError());
     } else {  // wino88d_out_half_kernel's Y, wino88d_in_kernel's fp64 V, the radix-256 slice kernel
         if (resid)
@@ -2729,7 +2484,7 @@ int kv_dev_wino88r_out(int device, const double* M, int rows, const float* scale
         KV_HIP(dv.alloc(nm));
         hipLaunchKernelGGL(kv::wino88d_in_kernel<512>, dim3(512 / 256, rows), dim3(256), 0, 0, dy.p, rows, dv.p);
         KV_HIP(hipGetLastError());
-        const int rc = launch_wino88i_slice<512, 4, double, 1, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
+        const int rc = launch_wino88i_slice<512, 4, double, true>(dv.p, rows, rows, kv::W88_XI, v8.p, ev.p, 0);
         if (rc) return rc;
     }
     KV_HIP(hipDeviceSynchronize());
@@ -2748,104 +2503,6 @@ __global__ void i8_fill_kernel(int8_t* d, size_t n_lines, int* e, size_t ne, uns
         d[i] = (int8_t)(dg == 0 ? (int)(h % 255u) - 127 : (int)(h % 129u) - 64);
     }
     if (i < ne) e[i] = (int)((i * 7u + seed) % 7u) - 3;
-}
-
-int kv_dev_i8gemm_bench(int device, int rows, int K, int variant, int iters, float* avg_us, float* M_out) {
-    KV_REQUIRE(rows > 0 && rows % 128 == 0 && rows <= kMaxBoards && (K == 256 || K == 512) && iters > 0 && avg_us,
-               KV_EINVAL, "kv_dev_i8gemm_bench: bad arguments");
-    KV_HIP(hipSetDevice(device));
-    const size_t lv = (size_t)kv::W88_XI * (K / 32) * rows, lu = (size_t)kv::W88_XI * (K / 32) * 512;
-    const size_t nm = (size_t)kv::W88_XI * rows * 512;
-    kv::DevBuf<int8_t> v8, u8;
-    kv::DevBuf<int> ev, eu;
-    kv::DevBuf<float> m;
-    KV_HIP(v8.alloc(lv * 128));
-    KV_HIP(u8.alloc(lu * 128));
-    KV_HIP(ev.alloc((size_t)kv::W88_XI * rows * 2));
-    KV_HIP(eu.alloc((size_t)kv::W88_XI * 512));
-    KV_HIP(m.alloc(nm));
-    hipLaunchKernelGGL(i8_fill_kernel, dim3((unsigned)((lv * 128 + 255) / 256)), dim3(256), 0, 0, v8.p, lv, ev.p,
-                       (size_t)kv::W88_XI * rows * 2, 1234u);
-    hipLaunchKernelGGL(i8_fill_kernel, dim3((unsigned)((lu * 128 + 255) / 256)), dim3(256), 0, 0, u8.p, lu, eu.p,
-                       (size_t)kv::W88_XI * 512, 99u);
-    KV_HIP(hipGetLastError());
-    constexpr int D = kv::kI8DigitsF32;
-    auto run = [&]() -> int {
-        const bool k5 = K == 512;
-        switch (variant) {
-            case 0: return k5 ? launch_wino88i_gemm<512, D>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0)
-                               : launch_wino88i_gemm<256, D>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0);
-            case 1: return k5 ? launch_wino88i32_gemm<512, 32, 3>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0)
-                              : launch_wino88i32_gemm<256, 32, 3>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            case 2: return k5 ? launch_wino88i32_gemm<512, 32, 3>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, false, 0)
-                              : launch_wino88i32_gemm<256, 32, 3>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, false, 0);
-            case 3: return k5 ? launch_wino88i32_gemm<512, 32, 4>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0)
-                              : launch_wino88i32_gemm<256, 32, 4>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            case 4: return k5 ? launch_wino88i32_gemm<512, 64, 2>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0)
-                              : launch_wino88i32_gemm<256, 64, 2>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            case 5: return k5 ? launch_wino88i32_gemm<512, 64, 2>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, false, 0)
-                              : launch_wino88i32_gemm<256, 64, 2>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, false, 0);
-            case 6:  // segment exponents (K 512): a different M from the same digits (timing only)
-                KV_REQUIRE(k5, KV_EINVAL, "kv_dev_i8gemm_bench: variant 6 needs K 512");
-                return launch_wino88i32_gemm<512, 32, 3, 2>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            case 7:  // ablation: variant 1 without the M stores (timing only)
-                KV_REQUIRE(k5, KV_EINVAL, "kv_dev_i8gemm_bench: variant 7 needs K 512");
-                return launch_wino88i32_gemm<512, 32, 3, 1, 1>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            case 8:  // ablation: variant 1 without the operand copies (timing only)
-                KV_REQUIRE(k5, KV_EINVAL, "kv_dev_i8gemm_bench: variant 8 needs K 512");
-                return launch_wino88i32_gemm<512, 32, 3, 1, 2>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            case 9:  // ablation: variant 4 (64-k stages) without the operand copies (timing only)
-                KV_REQUIRE(k5, KV_EINVAL, "kv_dev_i8gemm_bench: variant 9 needs K 512");
-                return launch_wino88i32_gemm<512, 64, 2, 1, 2>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            case 13:  // the round-4 kernel with the barrier in the middle of each stage
-                return k5 ? launch_wino88i32_gemm_mid<512>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0)
-                          : launch_wino88i32_gemm_mid<256>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0);
-            case 14:  // every wave lags h2 by a barrier (3 buffers)
-                return k5 ? launch_wino88i32_gemm_lag<512, false>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0)
-                          : launch_wino88i32_gemm_lag<256, false>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0);
-            case 15:  // staggered: waves 0-3 lag, 4-7 do not
-                return k5 ? launch_wino88i32_gemm_lag<512, true>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0)
-                          : launch_wino88i32_gemm_lag<256, true>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0);
-            case 16:  // every wave lags B digits 1-3 (12 MFMAs) by a barrier
-                return k5 ? launch_wino88i32_gemm_lag<512, false, 1>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0)
-                          : launch_wino88i32_gemm_lag<256, false, 1>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0);
-            case 18:  // four tiles per workgroup, the ring across them
-                return k5 ? launch_wino88i32_gemm_lagt<512, 4>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0)
-                          : launch_wino88i32_gemm_lagt<256, 4>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0);
-            case 19:  // five (2,048 rows: exactly 5 rounds)
-                return k5 ? launch_wino88i32_gemm_lagt<512, 5>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0)
-                          : launch_wino88i32_gemm_lagt<256, 5>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0);
-            case 17:  // every wave lags B digit 3 (2 MFMAs)
-                return k5 ? launch_wino88i32_gemm_lag<512, false, 3>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0)
-                          : launch_wino88i32_gemm_lag<256, false, 3>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0);
-            case 10:  // variant 1 with the M stores deferred past the next tile's first copies
-                return k5 ? launch_wino88i32_gemm<512, 32, 3, 1, 0, true>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0)
-                          : launch_wino88i32_gemm<256, 32, 3, 1, 0, true>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            case 11:  // variant 3 (4 buffers) deferred
-                return k5 ? launch_wino88i32_gemm<512, 32, 4, 1, 0, true>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0)
-                          : launch_wino88i32_gemm<256, 32, 4, 1, 0, true>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            case 12:  // variant 4 (64-k stages) deferred
-                return k5 ? launch_wino88i32_gemm<512, 64, 2, 1, 0, true>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0)
-                          : launch_wino88i32_gemm<256, 64, 2, 1, 0, true>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, true, 0);
-            default: KV_REQUIRE(false, KV_EINVAL, "kv_dev_i8gemm_bench: variant %d", variant);
-        }
-    };
-    int rc;
-    for (int w = 0; w < 2; ++w)
-        if ((rc = run())) return rc;
-    kv::DevEvent e0, e1;  // destroyed on every return path
-    KV_HIP(e0.create());
-    KV_HIP(e1.create());
-    KV_HIP(hipEventRecord(e0.e, 0));
-    for (int it = 0; it < iters; ++it)
-        if ((rc = run())) return rc;
-    KV_HIP(hipEventRecord(e1.e, 0));
-    KV_HIP(hipEventSynchronize(e1.e));
-    float ms = 0.f;
-    KV_HIP(hipEventElapsedTime(&ms, e0.e, e1.e));
-    *avg_us = 1000.f * ms / iters;
-    if (M_out) KV_HIP(hipMemcpy(M_out, m.p, nm * sizeof(float), hipMemcpyDeviceToHost));
-    return KV_OK;
 }
 
 // The in-kernel clock of the headline GEMM (MI355X_MICROARCH.md, DVFS give-back item 6): the product's fp32-tower
@@ -2907,7 +2564,7 @@ static int gemm_clock(int device, int rows, int digits, int abl, int share, doub
     };
     if (abl) KV_HIP(lds_opt_in((const void*)r3kern(false), bytes));
     auto launch = [&]() -> int {  // the product's launch, or the ablated kernel on the same grid
-        if (!abl) return i8f32_gemm<K>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, false, 0, r3, share);
+        if (!abl) return i8f32_gemm<K>(v8.p, ev.p, u8.p, eu.p, m.p, rows, rows, 0, r3, share);
         hipLaunchKernelGGL(r3kern(false), dim3(nwg), dim3(512), bytes, 0, v8.p, ev.p, u8.p, eu.p, m.p, rows, 512, rows,
                            nullptr);
         KV_HIP(hipGetLastError());
@@ -3020,16 +2677,16 @@ int kv_dev_out_phases(int device, int rows, int resid, int r3, unsigned long lon
         if (it == 3) KV_HIP(hipEventRecord(e0.e, 0));
         if (resid && r3)
             hipLaunchKernelGGL((kv::wino88i32_out_kernel<true, true, 512, true, true>), dim3(1, rows), dim3(1024), 0, 0,
-                               dm.p, rows, dsc.p, dsh.p, dy.p, dy.p, v8.p, ev.p, 0, 0);
+                               dm.p, rows, dsc.p, dsh.p, dy.p, dy.p, v8.p, ev.p);
         else if (resid)
             hipLaunchKernelGGL((kv::wino88i32_out_kernel<true, true, 512, false, true>), dim3(1, rows), dim3(1024), 0,
-                               0, dm.p, rows, dsc.p, dsh.p, dy.p, dy.p, v8.p, ev.p, 0, 0);
+                               0, dm.p, rows, dsc.p, dsh.p, dy.p, dy.p, v8.p, ev.p);
         else if (r3)
             hipLaunchKernelGGL((kv::wino88i32_out_kernel<false, false, 512, true, true>), dim3(1, rows), dim3(1024), 0,
-                               0, dm.p, rows, dsc.p, dsh.p, nullptr, nullptr, v8.p, ev.p, 0, 0);
+                               0, dm.p, rows, dsc.p, dsh.p, nullptr, nullptr, v8.p, ev.p);
         else
             hipLaunchKernelGGL((kv::wino88i32_out_kernel<false, false, 512, false, true>), dim3(1, rows), dim3(1024), 0,
-                               0, dm.p, rows, dsc.p, dsh.p, nullptr, nullptr, v8.p, ev.p, 0, 0);
+                               0, dm.p, rows, dsc.p, dsh.p, nullptr, nullptr, v8.p, ev.p);
         KV_HIP(hipGetLastError());
     }
     KV_HIP(hipEventRecord(e1.e, 0));

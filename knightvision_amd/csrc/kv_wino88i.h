@@ -180,10 +180,6 @@ __device__ inline unsigned i8_quad_transpose(unsigned P, int lane) {
     return __builtin_amdgcn_perm(r2, R, (lane & 2) ? 0x03020706u : 0x05040100u);
 }
 
-// CW channels per workgroup (2 CW threads: a plane split over lanes l, l ^ 32): 512 -- the row's exponent
-// over all its channels, one workgroup per board -- or 256 -- one exponent per 256-channel segment
-// (ex[(xi * 2 + seg) * rows + b]), two workgroups per board, so a CU holds two of them and one's loads
-// overlap the other's transforms and reductions.
 // The digits and exponent of `nslab` slabs of n rows of K fp64 values: row r of
 // slab x is src[(x * slab_rows + r) * K ...]; digit d of its channels
 // [32 kc, 32 kc + 32) goes to plane (x, kc, d) of dst -- 32 bytes at
@@ -191,19 +187,17 @@ __device__ inline unsigned i8_quad_transpose(unsigned P, int lane) {
 // ex[x * slab_rows + r]. One wave per row; lane l holds channels
 // [l * K/64, (l + 1) * K/64). RL (row lines, 4 digits only): digit d of the
 // 32 channels goes to (((x * K/32 + kc) * slab_rows + r) * 4 + d) * 32 instead
-// -- the 4 digits of one row's chunk are one 128-byte line. NSEG = 2 (K = 512 only): one exponent per
-// 256-channel segment instead of per row (lanes 0-31 hold segment 0), at ex[(x * 2 + seg) * slab_rows + r].
+// -- the 4 digits of one row's chunk are one 128-byte line.
 // R3 (KV_PATH_WINO88_I8F32R3; row lines): 3 radix-256 digits (i8_digits_r3) under the radix-256 exponent rule of
 // the fp32 or fp64 rows, in 96-byte lines (((x * K/32 + kc) * slab_rows + r) * 3 + d) * 32
-template <int K, class T, int D, bool RL = false, int NSEG = 1, bool R8 = false, bool R3 = false>
+template <int K, class T, int D, bool RL = false, bool R8 = false, bool R3 = false>
 __global__ __launch_bounds__(256) void wino88i_slice_kernel(const T* __restrict__ src, int n, int slab_rows,
                                                             int nslab, int8_t* __restrict__ dst,
                                                             int* __restrict__ ex) {
     static_assert(K == 256 || K == 512, "rows of 256 or 512 channels");
     static_assert(!RL || D == 4, "row lines hold 4 digits");
-    static_assert(NSEG == 1 || (NSEG == 2 && K == 512), "segments of 256 channels");
-    static_assert(!R8 || (D == 4 && sizeof(T) == 8 && NSEG == 1), "radix 256: 4 digits of fp64 rows");
-    static_assert(!R3 || (D == 4 && RL && NSEG == 1 && !R8), "3 radix-256 digits in 96-byte row lines");
+    static_assert(!R8 || (D == 4 && sizeof(T) == 8), "radix 256: 4 digits of fp64 rows");
+    static_assert(!R3 || (D == 4 && RL && !R8), "3 radix-256 digits in 96-byte row lines");
     constexpr int CPL = K / 64;  // 4 or 8 channels per lane
     const int lane = threadIdx.x & 63;
     const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -226,7 +220,7 @@ __global__ __launch_bounds__(256) void wino88i_slice_kernel(const T* __restrict_
         m = hw > m ? hw : m;
     }
 #pragma unroll
-    for (int o = 64 / (2 * NSEG); o > 0; o >>= 1) {
+    for (int o = 32; o > 0; o >>= 1) {
         const unsigned t = (unsigned)__shfl_xor((int)m, o, 64);
         m = t > m ? t : m;
     }
@@ -234,8 +228,7 @@ __global__ __launch_bounds__(256) void wino88i_slice_kernel(const T* __restrict_
                   : R3                              ? i8_row_exponent_f32r(m)
                   : sizeof(T) == 8                  ? i8_row_exponent(m)
                                                     : i8_row_exponent_f32(m);
-    if (NSEG == 1 && lane == 0) ex[row] = e;
-    if (NSEG == 2 && (lane & 31) == 0) ex[((size_t)x * 2 + (lane >> 5)) * slab_rows + r] = e;
+    if (lane == 0) ex[row] = e;
     unsigned long long pk[D] = {};
 #pragma unroll
     for (int i = 0; i < CPL; ++i) {
@@ -285,8 +278,6 @@ struct Wino88iTile {
     static constexpr int WM = WR * MT * 32, WN = WC * NT * 32;  // 128 x 128
     static constexpr int PLANE = 128 * 32;                      // bytes of one digit plane of a tile
     static constexpr int STAGE = 2 * D * PLANE;                 // A planes then B planes: 8 D KiB
-    static constexpr int NBUF = 3;
-    static constexpr size_t BYTES = (size_t)NBUF * STAGE;
     static constexpr int GL = STAGE / 1024 / (THREADS / 64);    // global_load_lds per wave and stage (= D)
 };
 
@@ -300,347 +291,39 @@ __device__ inline int i8_lds_half(int row, int h) { return 16 * (h ^ ((row >> 3)
 // ran 551 us against 523, profiles/r04_i8f32_rowlines_ab.log.)
 __device__ inline int i8_rl_off(int row, int chunk) { return row * 128 + 16 * (chunk ^ ((row >> 1) & 7)); }
 
-// M[xi] (fp64 [xi][stride rows][cout]) = V[xi] x U[xi]^T from the digits (see the header comment).
-// V8: planes [xi][K/32][5][stride][32], U8: [xi][K/32][5][cout][32]. XCD-aware tile order as kv_wino.h's
-// wino_gemm_kernel. RL (4 digits): row lines [xi][K/32][stride][4][32] and [xi][K/32][cout][4][32] -- a
-// stage of a tile is one contiguous 16 KiB block per operand, and one workgroup of the fused output
-// kernel (one board) writes whole lines.
-template <int K, int S, bool SPREAD = true, class OutT = double, bool RL = false>
-__global__ __launch_bounds__(512) void wino88i_gemm_kernel(const int8_t* __restrict__ V8,
-                                                            const int* __restrict__ ev,
-                                                            const int8_t* __restrict__ U8,
-                                                            const int* __restrict__ eu,
-                                                            OutT* __restrict__ M, int rows, int cout,
-                                                            int stride) {
-    constexpr int kI8Digits = S;  // digit planes per chunk = the levels kept
-    using T = Wino88iTile<S>;
-    constexpr int MT = T::MT, NT = T::NT, WM = T::WM, WN = T::WN, GL = T::GL;
-    constexpr int NK = K / 32;
-    static_assert(GL == S && GL * (T::THREADS / 64) * 1024 == T::STAGE, "stage split");
-    static_assert(!RL || S == 4, "row lines hold 4 digits");
-
-    extern __shared__ __attribute__((aligned(16))) i8x16_t lds_i8[];
-    char* const L0 = (char*)lds_i8;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / T::WC, wn = wave % T::WC;
-    const int CT = cout / WN, RT = rows / WM;
-    const int nwg = (int)gridDim.x;  // a multiple of 8
-    const int idx = (int)(blockIdx.x & 7) * (nwg >> 3) + (int)(blockIdx.x >> 3);
-    const int xi = idx / (CT * RT);
-    const int n_base = (idx % CT) * WN;
-    const int r_base = ((idx / CT) % RT) * WM;
-
-    // the GL pieces per stage of this wave: piece q = wave * GL + g covers operand q / 4S (V, U: the
-    // same for all of a wave's pieces), digit (q % 4S) / 4, rows 32 (q % 4) .. +31 of the tile; lane l
-    // fills LDS row 32 (q % 4) + l / 2, half l & 1 (bit 3 of that row is bit 4 of l). Everything but the
-    // lane's offset is wave-uniform.
-    const int op = (wave * GL) / (4 * S);
-    const size_t rstride = op ? (size_t)cout : (size_t)stride;
-    const size_t tbase = RL ? (op ? (size_t)n_base : (size_t)r_base) * 4 : (op ? n_base : r_base);  // RL: 128 B rows
-    const int8_t* gbase = op ? U8 + (((size_t)xi * NK) * kI8Digits * cout + tbase) * 32
-                             : V8 + (((size_t)xi * NK) * kI8Digits * stride + tbase) * 32;
-    const size_t sstep = (size_t)kI8Digits * rstride * 32;  // the next 32-k chunk
-    const int lane_off = (lane >> 1) * 32 + 16 * ((lane & 1) ^ ((lane >> 4) & 1));
-    // RL: piece q covers operand q / 16, rows 8 (q % 16) .. +7 (1 KiB contiguous in both places); lane l
-    // fills position l & 7 of LDS row 8 (q % 16) + l / 8 from source chunk (l & 7) ^ (row >> 1 & 7)
-    const int rl_off0 = (lane >> 3) * 128 + 16 * ((lane & 7) ^ (lane >> 4));
-    const int rl_off1 = (lane >> 3) * 128 + 16 * ((lane & 7) ^ (lane >> 4) ^ 4);
-    auto issue1 = [&](int g, int kt, int buf) {  // this wave's piece g of stage kt
-        const int q = wave * GL + g, d = (q % (4 * S)) / 4, rg = q % 4;
-        if constexpr (RL) {
-            const int rg8 = q % 16;
-            __builtin_amdgcn_global_load_lds(
-                (const void*)(gbase + kt * sstep + (size_t)rg8 * 1024 + ((rg8 & 1) ? rl_off1 : rl_off0)),
-                (__attribute__((address_space(3))) void*)(L0 + buf * T::STAGE + op * kI8Digits * T::PLANE +
-                                                          rg8 * 1024),
-                16, 0, 0);
-            return;
-        }
-        __builtin_amdgcn_global_load_lds(
-            (const void*)(gbase + kt * sstep + ((size_t)d * rstride + rg * 32) * 32 + lane_off),
-            (__attribute__((address_space(3))) void*)(L0 + buf * T::STAGE + op * kI8Digits * T::PLANE +
-                                                      d * T::PLANE + rg * 1024),
-            16, 0, 0);
-    };
-    auto issue = [&](int kt, int buf) {
-#pragma unroll
-        for (int g = 0; g < GL; ++g) issue1(g, kt, buf);
-    };
-
-    // fragments: A digit d of row r: plane d, row wm * 32 + (lane & 31), half lane >> 5 (swapped as stored)
-    const int lr = lane & 31, lh = lane >> 5;
-    const int arow = wm * 32 + lr;
-    const int aoff = arow * 32 + i8_lds_half(arow, lh);
-    int boff[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int bcol = wn * NT * 32 + nt * 32 + lr;
-        boff[nt] = kI8Digits * T::PLANE + bcol * 32 + i8_lds_half(bcol, lh);
-    }
-    // RL: the fragment of digit i is chunk 2 i + half of the row's line
-    int aoffr[S], boffr[NT][S];
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-        aoffr[i] = i8_rl_off(arow, 2 * i + lh);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-            boffr[nt][i] = kI8Digits * T::PLANE + i8_rl_off(wn * NT * 32 + nt * 32 + lr, 2 * i + lh);
-    }
-
-    i32x16_t acc[S][MT][NT];
-#pragma unroll
-    for (int l = 0; l < S; ++l)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[l][0][nt] = i32x16_t{};
-
-    issue(0, 0);
-    issue(1, 1);
-    for (int kt = 0; kt < NK; ++kt) {
-        // this wave's copies of stage kt have landed (stage kt + 1's may still be in flight), then
-        // every wave's have, and every wave is done reading the buffer stage kt + 2 goes into
-        if (kt + 1 < NK)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL) : "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        const char* buf = L0 + (kt % 3) * T::STAGE;
-        // the A digits (one 32-row block) stay live; B digit j (two 32-column blocks) dies after its
-        // S - j products, pairs i + j < S. Stage kt + 2's copies go out one per B digit, between the
-        // MFMA groups (issued back to back after the barrier they delayed every wave's first MFMA:
-        // profiles/r04_i8_glds_spread_ab.log)
-        i8x16_t a[S];
-#pragma unroll
-        for (int i = 0; i < S; ++i) a[i] = *(const i8x16_t*)(buf + (RL ? aoffr[i] : aoff + i * T::PLANE));
-#pragma unroll
-        for (int j = 0; j < S; ++j) {
-            i8x16_t b[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                b[nt] = *(const i8x16_t*)(buf + (RL ? boffr[nt][j] : boff[nt] + j * T::PLANE));
-#pragma unroll
-            for (int i = 0; i + j < S; ++i)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-                    acc[i + j][0][nt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b[nt], acc[i + j][0][nt], 0, 0, 0);
-            if (SPREAD && kt + 2 < NK) {
-#pragma unroll
-                for (int g = j * GL / S; g < (j + 1) * GL / S; ++g) issue1(g, kt + 2, (kt + 2) % 3);
-            }
-        }
-        if (!SPREAD && kt + 2 < NK) issue(kt + 2, (kt + 2) % 3);
-    }
-
-    // D: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) inside the 32 x 32 block
-    const int* evx = ev + (size_t)xi * stride + r_base + wm * 32;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int col = n_base + wn * NT * 32 + nt * 32 + lr;
-        const int ec = eu[(size_t)xi * cout + col] - 14;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            double m = (double)acc[S - 1][0][nt][r];
-#pragma unroll
-            for (int l = S - 2; l >= 0; --l) m = __builtin_fma(m, 0.0078125, (double)acc[l][0][nt][r]);  // exact
-            M[((size_t)xi * stride + r_base + wm * 32 + row) * cout + col] = (OutT)ldexp(m, evx[row] + ec);
-        }
-    }
-}
-
-// wino88i_gemm_kernel<K, 4, ., float, true> with the stage barrier moved to the middle of the stage
-// (MID): a stage's MFMAs run in two halves (B digits 0-1: 14 of its 20 MFMAs per wave; 2-3: 6), and between
-// them the waves wait for the NEXT stage's copies, pass one barrier, and read that stage's A digits and first
-// B digit -- so those LDS reads run under the second half's MFMAs instead of after a barrier with both waves
-// of a SIMD idle. The ring has 4 buffers: stage kt + 3's copies go out after the barrier in the middle of
-// stage kt (all waves are then past stage kt - 1, whose buffer they refill), two per B digit of the second
-// half. Same products, same k order, same bits.
-template <int K>
-__global__ __launch_bounds__(512) void wino88i32_gemm_mid_kernel(const int8_t* __restrict__ V8,
-                                                                 const int* __restrict__ ev,
-                                                                 const int8_t* __restrict__ U8,
-                                                                 const int* __restrict__ eu, float* __restrict__ M,
-                                                                 int rows, int cout, int stride) {
-    constexpr int S = 4, NBUF = 4;
-    using T = Wino88iTile<S>;
-    constexpr int NT = T::NT, WM = T::WM, WN = T::WN, GL = T::GL;
-    constexpr int NK = K / 32;
-    static_assert(GL == 4 && NK >= 4, "4 pieces per wave and stage");
-
-    extern __shared__ __attribute__((aligned(16))) i8x16_t lds_i8m[];
-    char* const L0 = (char*)lds_i8m;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / T::WC, wn = wave % T::WC;
-    const int CT = cout / WN, RT = rows / WM;
-    const int nwg = (int)gridDim.x;  // a multiple of 8
-    const int idx = (int)(blockIdx.x & 7) * (nwg >> 3) + (int)(blockIdx.x >> 3);
-    const int xi = idx / (CT * RT);
-    const int n_base = (idx % CT) * WN;
-    const int r_base = ((idx / CT) % RT) * WM;
-
-    // copy pieces as wino88i_gemm_kernel's row-line path: piece q = wave * 4 + g covers operand q / 16,
-    // rows 8 (q % 16) .. +7
-    const int op = (wave * GL) / (4 * S);
-    const size_t rstride = op ? (size_t)cout : (size_t)stride;
-    const int8_t* gbase = op ? U8 + (((size_t)xi * NK) * cout + (size_t)n_base) * 128
-                             : V8 + (((size_t)xi * NK) * stride + (size_t)r_base) * 128;
-    const size_t sstep = rstride * 128;
-    const int rl_off0 = (lane >> 3) * 128 + 16 * ((lane & 7) ^ (lane >> 4));
-    const int rl_off1 = (lane >> 3) * 128 + 16 * ((lane & 7) ^ (lane >> 4) ^ 4);
-    auto issue1 = [&](int g, int kt) {
-        const int q = wave * GL + g, rg8 = q % 16;
-        __builtin_amdgcn_global_load_lds(
-            (const void*)(gbase + kt * sstep + (size_t)rg8 * 1024 + ((rg8 & 1) ? rl_off1 : rl_off0)),
-            (__attribute__((address_space(3))) void*)(L0 + (kt % NBUF) * T::STAGE + op * S * T::PLANE + rg8 * 1024),
-            16, 0, 0);
-    };
-
-    const int lr = lane & 31, lh = lane >> 5;
-    const int arow = wm * 32 + lr;
-    int aoffr[S], boffr[NT][S];
-#pragma unroll
-    for (int i = 0; i < S; ++i) {
-        aoffr[i] = i8_rl_off(arow, 2 * i + lh);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) boffr[nt][i] = S * T::PLANE + i8_rl_off(wn * NT * 32 + nt * 32 + lr, 2 * i + lh);
-    }
-
-    i32x16_t acc[S][NT];
-#pragma unroll
-    for (int l = 0; l < S; ++l)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[l][nt] = i32x16_t{};
-
-    // prologue: stages 0-2 in flight, stage 0 landed (this wave's copies, then every wave's), its A digits
-    // and first B digit read
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int g = 0; g < GL; ++g) issue1(g, k);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GL) : "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    i8x16_t a[S], b0[NT];
-#pragma unroll
-    for (int i = 0; i < S; ++i) a[i] = *(const i8x16_t*)(L0 + aoffr[i]);
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) b0[nt] = *(const i8x16_t*)(L0 + boffr[nt][0]);
-
-    for (int kt = 0; kt < NK; ++kt) {
-        const char* buf = L0 + (kt % NBUF) * T::STAGE;
-        i8x16_t b1[NT], b2[NT], b3[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) b1[nt] = *(const i8x16_t*)(buf + boffr[nt][1]);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                acc[i][nt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b0[nt], acc[i][nt], 0, 0, 0);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) b2[nt] = *(const i8x16_t*)(buf + boffr[nt][2]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                acc[i + 1][nt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b1[nt], acc[i + 1][nt], 0, 0, 0);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) b3[nt] = *(const i8x16_t*)(buf + boffr[nt][3]);
-        // the A digits of stage kt that the second half still needs (i = 0, 1), before they are replaced
-        const i8x16_t a0 = a[0], a1 = a[1];
-        // middle: stage kt + 1 landed (only stage kt + 2's copies may still be in flight), then every wave
-        // is past stage kt - 1, whose buffer stage kt + 3's copies refill
-        if (kt + 1 < NK) {
-            if (kt + 2 < NK)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL) : "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (kt + 1 < NK) {
-            const char* nb = L0 + ((kt + 1) % NBUF) * T::STAGE;
-#pragma unroll
-            for (int i = 0; i < S; ++i) a[i] = *(const i8x16_t*)(nb + aoffr[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                acc[i + 2][nt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(i ? a1 : a0, b2[nt], acc[i + 2][nt], 0, 0, 0);
-        if (kt + 3 < NK) {
-            issue1(0, kt + 3);
-            issue1(1, kt + 3);
-        }
-        if (kt + 1 < NK) {
-            const char* nb = L0 + ((kt + 1) % NBUF) * T::STAGE;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) b0[nt] = *(const i8x16_t*)(nb + boffr[nt][0]);
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-            acc[3][nt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, b3[nt], acc[3][nt], 0, 0, 0);
-        if (kt + 3 < NK) {
-            issue1(2, kt + 3);
-            issue1(3, kt + 3);
-        }
-    }
-
-    // epilogue (as wino88i_gemm_kernel's): D col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    const int* evx = ev + (size_t)xi * stride + r_base + wm * 32;
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int col = n_base + wn * NT * 32 + nt * 32 + lr;
-        const int ec = eu[(size_t)xi * cout + col] - 14;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            double m = (double)acc[S - 1][nt][r];
-#pragma unroll
-            for (int l = S - 2; l >= 0; --l) m = __builtin_fma(m, 0.0078125, (double)acc[l][nt][r]);  // exact
-            M[((size_t)xi * stride + r_base + wm * 32 + row) * cout + col] = (float)ldexp(m, evx[row] + ec);
-        }
-    }
-}
-
-// The same GEMM as one loop over stage barriers in which a wave's MFMAs for stage k are split in two
-// halves: h1(k) = B digits 0-1 (14 of 20 MFMAs per wave), h2(k) = B digits 2-3 (6). Two programs:
-//   LAG ("mid"): after barrier k it reads stage k's A digits and first B digit while it runs h2(k - 1)
-//     from registers (the A digits 0-1 and B digits 2-3 of stage k - 1, kept), then h1(k);
-//   plain: after barrier k it reads stage k's digits and runs h1(k) and h2(k).
-// Either way every LDS read of stage k happens between barriers k and k + 1, so stage k + 2's copies go into
-// stage k - 1's buffer right after barrier k (3 buffers, two stages in flight). STAG: waves 0-3 lag, waves
-// 4-7 do not -- the two waves of a SIMD then reach each barrier at different points of their MFMA streams
-// (one finishing a stage, one mid-stage), so one issues MFMAs while the other waits on its LDS reads; else
-// every wave lags. Same products, same bits.
+// The fp32 tower's GEMM on 4 digits in row lines: M[xi] (fp32 [xi][stride rows][cout]) = V[xi] x U[xi]^T from the
+// digits (see the header comment). V8: row lines [xi][K/32][stride][4][32], U8: [xi][K/32][cout][4][32] -- a
+// stage of a tile is one contiguous 16 KiB block per operand, and one workgroup of the fused output kernel (one
+// board) writes whole lines. XCD-aware tile order as kv_wino.h's wino_gemm_kernel. One loop over stage barriers
+// in which a wave's MFMAs for stage k are split in two halves: h1(k) = B digits 0-1 (14 of 20 MFMAs per wave),
+// h2(k) = B digits 2-3 (6). After barrier k a wave reads stage k's A digits and first B digit while it runs
+// h2(k - 1) from registers (the A digits 0-1 and B digits 2-3 of stage k - 1, kept), then h1(k). Every LDS read
+// of stage k happens between barriers k and k + 1, so stage k + 2's copies go into stage k - 1's buffer right
+// after barrier k (3 buffers, two stages in flight).
 #ifndef KV_LAG_OPAQUE
 // 1: the lagging operands redefined opaquely after the pre-barrier lgkmcnt(0) (so the compiler's waitcnt pass
 // cannot make the first lagging MFMA wait for the new stage's LDS reads). Bit-identical either way; measured
 // (profiles/r06_gemm_opaque_lj_ab.log) neutral on the 4-digit tower and 0.6-1.5 % slower forward on R3: off.
 #define KV_LAG_OPAQUE 0
 #endif
-template <int K, bool STAG, int LJ = 2>
+template <int K>
 __global__ __launch_bounds__(512) void wino88i32_gemm_lag_kernel(const int8_t* __restrict__ V8,
                                                                  const int* __restrict__ ev,
                                                                  const int8_t* __restrict__ U8,
                                                                  const int* __restrict__ eu, float* __restrict__ M,
                                                                  int rows, int cout, int stride) {
-    constexpr int S = 4, NBUF = 3;
+    constexpr int S = 4, NBUF = 3, LJ = 2;  // B digits LJ.. lag
     using T = Wino88iTile<S>;
     constexpr int NT = T::NT, WM = T::WM, WN = T::WN, GL = T::GL;
     constexpr int NK = K / 32;
     constexpr int NA = S - LJ;  // A digits the lagging half uses (0 .. S - LJ - 1)
-    static_assert(GL == 4 && NK >= 3 && LJ >= 1 && LJ <= 3, "4 pieces per wave and stage; B digits LJ.. lag");
+    static_assert(GL == 4 && NK >= 3, "4 pieces per wave and stage");
 
     extern __shared__ __attribute__((aligned(16))) i8x16_t lds_i8l[];
     char* const L0 = (char*)lds_i8l;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
-    const bool lag = !STAG || wave < 4;  // wave-uniform
     const int wm = wave / T::WC, wn = wave % T::WC;
     const int CT = cout / WN, RT = rows / WM;
     const int nwg = (int)gridDim.x;  // a multiple of 8
@@ -717,7 +400,7 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_lag_kernel(const int8_t* _
         for (int i = 0; i < S; ++i) a[i] = *(const i8x16_t*)(buf + aoffr[i]);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) b[0][nt] = *(const i8x16_t*)(buf + boffr[nt][0]);
-        if (lag && kt > 0) h2(pa, pb);  // under the reads above
+        if (kt > 0) h2(pa, pb);  // under the reads above
         // stage kt + 2 into stage kt - 1's buffer, two pieces at the start, two after the first B digit
         if (kt + 2 < NK) {
             issue1(0, kt + 2);
@@ -747,11 +430,10 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_lag_kernel(const int8_t* _
         for (int j = LJ; j < S; ++j)
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) pb[j - LJ][nt] = b[j][nt];
-        if (!lag) h2(pa, pb);  // h2(kt) now
     }
-    if (lag) h2(pa, pb);
+    h2(pa, pb);
 
-    // epilogue (as wino88i_gemm_kernel's): D col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    // epilogue: D col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     const int* evx = ev + (size_t)xi * stride + r_base + wm * 32;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -991,14 +673,8 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_lagt_kernel(const int8_t* 
     }
 }
 
-template <int ABL>
 __device__ __forceinline__ i32x16_t r3mfma(i8x16_t a, i8x16_t b, i32x16_t c) {
-    if constexpr ((ABL & 2) != 0) {  // ablation: the fragments are consumed, no MFMA issues
-        asm volatile("" ::"v"(a), "v"(b));
-        return c;
-    } else {
-        return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
-    }
+    return __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c, 0, 0, 0);
 }
 // R3's GEMM (KV_PATH_WINO88_I8F32R3) with 64-k stages: the 32-k lagt kernel gives a wave 12 MFMAs per stage
 // barrier at 3 digits (20 at 4), and its time did not move with 3, 4 or 5 ring buffers (370.6 / 371.3 / 371.6
@@ -1018,10 +694,9 @@ __device__ __forceinline__ i32x16_t r3mfma(i8x16_t a, i8x16_t b, i32x16_t c) {
 // between half 1's last 9 MFMAs, placed by sched_group_barrier; half 1's epilogue follows the stage. The
 // epilogue's stores address a wave-uniform 64-bit tile base plus a 32-bit lane offset. Exposed epilogue (the kernel
 // against ABL 16): 66 of 346 us at 2,048 rows before this, profiles/r3_gemm_epilogue_ab.log.
-// ABL (timing ablations, outputs invalid; never the product's): 1 no copies after the prologue, 2 no MFMAs (the
-// fragments still read), 4 no M stores, 8 no exponent loads in the epilogue, 16 no epilogue at all (the
-// accumulators consumed by an opaque use; kv_dev_r3gemm_clock only). With 4 or 16 the waits allow no M stores in
-// flight. KV_R3_M_NT (1): M stored non-temporally -- the GEMM 339 -> 325 us, the
+// ABL 16 (a timing ablation, outputs invalid; never the product's, kv_dev_r3gemm_clock only): no epilogue at all,
+// the accumulators consumed by an opaque use, and the waits allow no M stores in flight.
+// KV_R3_M_NT (1): M stored non-temporally -- the GEMM 339 -> 325 us, the
 // output kernels that read it +2 %, forward -1.5 % at 2,048 boards, neutral at 256 (profiles/r06_mnt_ab.log).
 #ifndef KV_R3_M_NT
 #define KV_R3_M_NT 1
@@ -1048,7 +723,8 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
     // MFMAs (below). Not with one tile per workgroup: that form gains nothing from it (its two workgroups per CU
     // run out of step already) and the compiler spills registers there
     constexpr bool SPLIT = TPW > 1;
-    constexpr int MST = (ABL & (4 | 16)) ? 0 : 32;  // M stores a tile's epilogue leaves in flight (none: ablated)
+    static_assert(ABL == 0 || ABL == 16, "the product, or the no-epilogue ablation");
+    constexpr int MST = ABL == 16 ? 0 : 32;  // M stores a tile's epilogue leaves in flight (none: ablated)
 
     extern __shared__ __attribute__((aligned(16))) i8x16_t lds_i8k64[];
     char* const L0 = (char*)lds_i8k64;
@@ -1088,8 +764,6 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
     }
     const int ldst = (op * 2 + chunk) * PLANE + pp0 * 1024;
     auto issue1 = [&](int g, int s, int sg) {  // piece g of the group's stage s (tile s / NU), ring stage sg
-        if constexpr ((ABL & 1) != 0)
-            if (sg >= PD) return;
         const int j = s / NU, ku = s - j * NU;
         const int8_t* base = gb[0];
 #pragma unroll
@@ -1171,7 +845,7 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
                 for (int i = 0; i + jb < ND; ++i)
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt)
-                        acc[i + jb][nt] = r3mfma<ABL>(pa[i], pb[jb - 1][nt], acc[i + jb][nt]);
+                        acc[i + jb][nt] = r3mfma(pa[i], pb[jb - 1][nt], acc[i + jb][nt]);
         };
         // M addresses: one wave-uniform 64-bit base per tile plus this lane's unsigned 32-bit byte offset mlo inside
         // the wave's 32 x 64 block (< 128 cout 4 = 256 KiB); a row or column half of the block is a wave-uniform
@@ -1179,18 +853,16 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
         float* const Mt = M + ((size_t)xis[j] * stride + rbs[j] + wu / WC * 32) * cout + nbs[j] + wu % WC * NT * 32;
         const int* const evx = exg + j * 256 + wm * 32;  // LDS (staged below)
         auto epi = [&](int nt) {  // column half nt of the tile: the three levels combined (exact), one rounding
-            const int ec = (ABL & 8) ? -14 : exg[j * 256 + 128 + wn * NT * 32 + nt * 32 + lr] - 14;
+            const int ec = exg[j * 256 + 128 + wn * NT * 32 + nt * 32 + lr] - 14;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int rowu = (r & 3) + 8 * (r >> 2), row = rowu + 4 * lh;
                 double mm = (double)acc[ND - 1][nt][r];
 #pragma unroll
                 for (int l = ND - 2; l >= 0; --l) mm = __builtin_fma(mm, kStep, (double)acc[l][nt][r]);  // exact
-                const float o = (float)ldexp(mm, ((ABL & 8) ? 0 : evx[row]) + ec);
+                const float o = (float)ldexp(mm, evx[row] + ec);
                 float* const mp = (float*)((char*)(Mt + (size_t)rowu * cout + nt * 32) + mlo);
-                if constexpr ((ABL & 4) != 0)
-                    asm volatile("" ::"v"(o));
-                else if constexpr (KV_R3_M_NT)
+                if constexpr (KV_R3_M_NT)
                     __builtin_nontemporal_store(o, mp);
                 else
                     *mp = o;
@@ -1241,7 +913,7 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
                 for (int i = 0; i + jb < ND; ++i)
 #pragma unroll
                     for (int nt = 0; nt < (last && jb > 0 ? 1 : NT); ++nt)  // last: nt 1's come below
-                        acc[i + jb][nt] = r3mfma<ABL>(a0[i], b0[jb][nt], acc[i + jb][nt]);
+                        acc[i + jb][nt] = r3mfma(a0[i], b0[jb][nt], acc[i + jb][nt]);
                 if (jb == 0 && sg + PD < NST) {
                     issue1(3, s + PD, sg + PD);
                     issue1(4, s + PD, sg + PD);
@@ -1263,23 +935,23 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
                 // into the same exact int32 levels, so the same bits; every store still issues before the next
                 // tile's first wait, so no wait count changes
 #pragma unroll
-                for (int i = 0; i < ND; ++i) acc[i][0] = r3mfma<ABL>(a1[i], b1[0][0], acc[i][0]);
+                for (int i = 0; i < ND; ++i) acc[i][0] = r3mfma(a1[i], b1[0][0], acc[i][0]);
 #pragma unroll
                 for (int jb = 1; jb < ND; ++jb)
 #pragma unroll
-                    for (int i = 0; i + jb < ND; ++i) acc[i + jb][0] = r3mfma<ABL>(a1[i], b1[jb][0], acc[i + jb][0]);
+                    for (int i = 0; i + jb < ND; ++i) acc[i + jb][0] = r3mfma(a1[i], b1[jb][0], acc[i + jb][0]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int jb = 1; jb < ND; ++jb)
 #pragma unroll
-                    for (int i = 0; i + jb < ND; ++i) acc[i + jb][1] = r3mfma<ABL>(a0[i], b0[jb][1], acc[i + jb][1]);
+                    for (int i = 0; i + jb < ND; ++i) acc[i + jb][1] = r3mfma(a0[i], b0[jb][1], acc[i + jb][1]);
 #pragma unroll
-                for (int i = 0; i < ND; ++i) acc[i][1] = r3mfma<ABL>(a1[i], b1[0][1], acc[i][1]);
+                for (int i = 0; i < ND; ++i) acc[i][1] = r3mfma(a1[i], b1[0][1], acc[i][1]);
 #pragma unroll
                 for (int jb = 1; jb < ND; ++jb)
 #pragma unroll
-                    for (int i = 0; i + jb < ND; ++i) acc[i + jb][1] = r3mfma<ABL>(a1[i], b1[jb][1], acc[i + jb][1]);
-                if constexpr ((ABL & (2 | 16)) == 0) {
+                    for (int i = 0; i + jb < ND; ++i) acc[i + jb][1] = r3mfma(a1[i], b1[jb][1], acc[i + jb][1]);
+                if constexpr (ABL != 16) {
                     epi(0);
 #pragma unroll
                     for (int q = 0; q < 9; ++q) {  // per MFMA: 16 VALU issues (two values' worth), two of the 16 stores
@@ -1294,7 +966,7 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
                 for (int i = 0; i < ND; ++i)
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt)
-                        acc[i][nt] = r3mfma<ABL>(a1[i], b1[0][nt], acc[i][nt]);
+                        acc[i][nt] = r3mfma(a1[i], b1[0][nt], acc[i][nt]);
                 pa[0] = a1[0];
                 pa[1] = a1[1];
 #pragma unroll
@@ -1310,13 +982,13 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
             }
         }
         if constexpr (!SPLIT) h2();
-        if constexpr ((ABL & 16) != 0) {  // ablation: no epilogue, the accumulators consumed by an opaque use
+        if constexpr (ABL == 16) {  // ablation: no epilogue, the accumulators consumed by an opaque use
 #pragma unroll
             for (int l = 0; l < ND; ++l)
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) asm volatile("" ::"v"(acc[l][nt]));
         } else {
-            if constexpr (!SPLIT || (ABL & 2) != 0) epi(0);
+            if constexpr (!SPLIT) epi(0);
             epi(1);
         }
     }
@@ -1333,7 +1005,8 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_r3k64_kernel(const int8_t*
 // KV_PREC_I8X5's GEMM (5 digits, digit planes, fp64 M) with wino88i32_gemm_lag_kernel's schedule: the
 // B digits j >= LJ of a stage (their pairs i + j <= 4) run after the next barrier, under that stage's first
 // LDS reads; stage k + 2's copies (5 pieces per wave) go into stage k - 1's buffer right after barrier k.
-// Same products, same bits as wino88i_gemm_kernel<K, 5, ., double>.
+// V8: planes [xi][K/32][5][stride][32], U8: [xi][K/32][5][cout][32]; M fp64 [xi][stride rows][cout]. Exact int32
+// levels, one exact fp64 combine: the bits of tests/_i8_digits' restatement, whatever the schedule.
 // S = 4, RB = 8 (KV_PATH_WINO88_I8R): 4 radix-256 digit planes per operand (4 pieces per wave and stage), the
 // 13 pairs i + j <= 4 of 16 -- the same 5 levels, weighted 2^-8l -- combined in fp64 (the last two fma steps
 // may round: |level| <= 4 K 2^14 = 2^25, so the value has up to 57 significant bits; one fp64 rounding each).
@@ -1367,7 +1040,7 @@ __global__ __launch_bounds__(512) void wino88i_gemm_lag5_kernel(const int8_t* __
     const int n_base = (idx % CT) * WN;
     const int r_base = ((idx / CT) % RT) * WM;
 
-    // copy pieces as wino88i_gemm_kernel's planes path: piece q = wave * S + g covers operand q / 4S, digit
+    // copy pieces of the planes path: piece q = wave * S + g covers operand q / 4S, digit
     // (q % 4S) / 4, rows 32 (q % 4) .. +31; lane l fills LDS row 32 (q % 4) + l / 2, half l & 1 (swapped on
     // bit 3 of the row)
     const int op = (__builtin_amdgcn_readfirstlane(wave) * GL) / (4 * S);  // wave-uniform
@@ -1491,7 +1164,7 @@ __global__ __launch_bounds__(512) void wino88i_gemm_lag5_kernel(const int8_t* __
     }
     h2();
 
-    // epilogue (as wino88i_gemm_kernel's): D col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    // epilogue: D col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
     const int* evx = ev + (size_t)xi * stride + r_base + wm * 32;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
@@ -1622,285 +1295,6 @@ __global__ __launch_bounds__(256) void wino88i_in_kernel(const float* __restrict
     }
 }
 
-// ---- the fp32 tower's GEMM on 4 int8 digits, round 5 (wino88i32_gemm_kernel) ----
-// The same products as wino88i_gemm_kernel<K, 4, ., float, true> -- exact int32 levels, one rounding to fp32 --
-// with four changes, none of which changes a bit of M:
-//  * operands swapped: A = U (32 output channels per wave), B = V (2 x 32 boards), so the accumulator's 4
-//    consecutive registers are 4 consecutive output channels of one board and the epilogue writes M with
-//    16-byte stores (8 per wave instead of 32 dword stores);
-//  * the level combine in integers first: H = 128 L0 + L1 and L = 128 L2 + L3 are exact in int32 (|L0| <=
-//    K 127^2 < 2^23, |L1| <= 2 K 127 64, |L2| <= K (2 127 64 + 64^2), |L3| <= K (2 127 64 + 2 64^2), all at
-//    K = 512), then m = 2^14 H + L in fp64 (< 2^46: exact) -- the same value as the fp64 chain
-//    L0 + L1/128 + L2/128^2 + L3/128^3 times 2^21, so the same fp32 after ldexp and the one rounding;
-//  * persistent workgroups: one per CU, each walking a contiguous run of its XCD's share of the tile order
-//    (the XCD-aware order of wino88i_gemm_kernel), with the copy ring running across tiles -- the next tile's
-//    first stages are in flight during this tile's last stages and its epilogue;
-//  * the row exponents of a tile (128 of V, 128 of U) come into LDS by one more global_load_lds piece with
-//    the tile's first stage and are read into registers after that stage's barrier (an ordinary load's
-//    first use, or an LDS read in the epilogue, makes hipcc wait vmcnt(0) on the ring).
-// KS: k per stage (32 or 64: one barrier per KS), NBUF: ring buffers (prefetch distance NBUF - 1).
-template <int KS, int NBUF>
-struct I8G32 {
-    static constexpr int THREADS = 512, WM = 128, WN = 128;  // WM output channels x WN boards
-    static constexpr int NCH = KS / 32;                      // 32-k chunks per stage
-    static constexpr int CHB = 128 * 128;                    // one operand's chunk: 128 rows x 128-B lines
-    static constexpr int STAGE = 2 * NCH * CHB;              // [op U, V][chunk][row][128 B]
-    static constexpr int GL = STAGE / 1024 / (THREADS / 64); // global_load_lds pieces per wave and stage
-    static constexpr int EXP = NBUF * STAGE;                 // 2 x 2 KiB of exponents (tile parity)
-    static constexpr size_t BYTES = (size_t)NBUF * STAGE + 4096;
-    static constexpr int NS = 8;                             // epilogue stores per wave
-};
-
-// NSEG: V's exponents per 256-channel segment (K / 256 of them, ev[(xi * NSEG + seg)][row]: the output
-// kernel that writes V sees 256 channels of a board) instead of per row (1). Each segment's levels are
-// combined exactly (2^14 H + L, fp64) and scaled by its exponent; the segments' scaled values add in fp64 in
-// segment order (one fp64 rounding, 2^-53: deterministic, so still batch-invariant), then the one rounding to
-// fp32. NSEG = 1 is bit-identical to wino88i_gemm_kernel.
-// ABL (timing ablations of kv_dev_i8gemm_bench only; M is wrong): 1 no M stores (the values kept live),
-// 2 no operand copies (the waits and barriers stay; LDS holds whatever it held).
-// DEFER: a tile's 8 M stores per wave wait in registers until the next tile's first stage has issued its
-// copies, so no vmcnt wait of the next tile's first PD + 1 stages has to retire them (the stores are older
-// than every copy such a wait needs otherwise; vmcnt counts in issue order).
-template <int K, int KS, int NBUF, int NSEG = 1, int ABL = 0, bool DEFER = false>
-__global__ __launch_bounds__(512) void wino88i32_gemm_kernel(const int8_t* __restrict__ V8,
-                                                             const int* __restrict__ ev,
-                                                             const int8_t* __restrict__ U8,
-                                                             const int* __restrict__ eu, float* __restrict__ M,
-                                                             int rows, int stride) {
-    using T = I8G32<KS, NBUF>;
-    constexpr int NK = K / KS, NCH = T::NCH, GL = T::GL, PD = NBUF - 1;
-    static_assert(GL * 8 * 1024 == T::STAGE && GL % 4 == 0, "stage split");
-    static_assert(NSEG == 1 || (NSEG == 2 && K == 512 && NK % 2 == 0), "256-channel segments");
-    constexpr int NEP = NSEG == 1 ? 1 : 2;  // exponent pieces per tile (items of 128 ints: ev segs, eu)
-    extern __shared__ __attribute__((aligned(16))) i8x16_t lds_i8g[];
-    char* const L0 = (char*)lds_i8g;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;  // 32 output channels, 64 boards
-    const int RT = rows / T::WN, CT = 512 / T::WM;
-    const int ntiles = kv::W88_XI * RT * CT;
-    // this workgroup's tiles: XCD group x = blockIdx % 8 owns [x T8, (x + 1) T8) of the tile order; its P
-    // workgroups take every P-th tile of that run (gridDim = ntiles: one tile each, the plain XCD order)
-    const int T8 = ntiles >> 3, P = (int)gridDim.x >> 3;
-    const int tfirst = (int)(blockIdx.x & 7) * T8 + (int)(blockIdx.x >> 3);
-    const int tend = (int)(blockIdx.x & 7) * T8 + T8;
-    const int ntile_wg = tfirst < tend ? (tend - tfirst + P - 1) / P : 0;
-    const int nstage = ntile_wg * NK;
-
-    // piece q = wave * GL + g: operand q / (16 NCH) (U: waves 0-3, V: waves 4-7), chunk (q / 16) % NCH,
-    // rows 8 (q % 16) .. +7; lane l fills position l & 7 of LDS row 8 (q % 16) + l / 8 from source chunk
-    // (l & 7) ^ (row >> 1 & 7) (the row-line image of wino88i_gemm_kernel)
-    const int op = wave >> 2;
-    const int rl_off0 = (lane >> 3) * 128 + 16 * ((lane & 7) ^ (lane >> 4));
-    const int rl_off1 = (lane >> 3) * 128 + 16 * ((lane & 7) ^ (lane >> 4) ^ 4);
-    const size_t cstride = (size_t)(op ? stride : 512) * 128;  // the next 32-k chunk of an operand
-    auto tile_of = [&](int n, int& xi, int& n_base, int& r_base) {  // n-th tile of this workgroup
-        const int idx = tfirst + n * P;
-        xi = idx / (CT * RT);
-        n_base = (idx % CT) * T::WM;
-        r_base = ((idx / CT) % RT) * T::WN;
-    };
-    // a tile's operand base (this wave's operand) and exponent-piece sources: item i of the exponent slot
-    // (128 ints at byte 512 i) is ev of segment i for i < NSEG, then eu (repeated to fill the last piece);
-    // piece p carries items 2p (lanes 0-31) and 2p + 1 (lanes 32-63)
-    auto tile_base = [&](int n, const int8_t*& gb, const int* (&es)[NEP]) {
-        int xi, n_base, r_base;
-        tile_of(n, xi, n_base, r_base);
-        gb = op ? V8 + (((size_t)xi * (K / 32)) * stride + r_base) * 128
-                : U8 + (((size_t)xi * (K / 32)) * 512 + n_base) * 128;
-#pragma unroll
-        for (int p = 0; p < NEP; ++p) {
-            const int item = 2 * p + (lane >> 5);
-            const bool isv = item < NSEG;
-            es[p] = (isv ? ev : eu) + (isv ? ((size_t)xi * NSEG + item) * stride + r_base
-                                           : (size_t)xi * 512 + n_base) + 4 * (lane & 31);
-        }
-    };
-    // pieces g0 .. g1 - 1 of stage kt of the tile at gb (exponents first when ex != nullptr), into buffer buf
-    auto issue = [&](const int8_t* gb, int kt, int buf, int g0, int g1) {
-        if (ABL == 2) return;
-        const int8_t* gk = gb + (size_t)(kt * NCH) * cstride;
-#pragma unroll
-        for (int g = g0; g < g1; ++g) {
-            const int q = wave * GL + g, rg8 = q % 16, ch = (q / 16) % NCH;
-            __builtin_amdgcn_global_load_lds(
-                (const void*)(gk + (size_t)ch * cstride + (size_t)rg8 * 1024 + ((rg8 & 1) ? rl_off1 : rl_off0)),
-                (__attribute__((address_space(3))) void*)(L0 + buf * T::STAGE + (op * NCH + ch) * T::CHB +
-                                                          rg8 * 1024),
-                16, 0, 0);
-        }
-    };
-    auto issue_exp = [&](const int* const* es, int n) {
-#pragma unroll
-        for (int p = 0; p < NEP; ++p)
-            __builtin_amdgcn_global_load_lds(
-                (const void*)es[p], (__attribute__((address_space(3))) void*)(L0 + T::EXP + (n & 1) * 2048 + p * 1024),
-                16, 0, 0);
-    };
-
-    // fragments: A = U digit i of channel row wm * 32 + (lane & 31), B = V digit j of board row
-    // wn * 64 + nt * 32 + (lane & 31); the 16-byte chunk 2 i + (lane >> 5) of the row's line
-    const int lr = lane & 31, lh = lane >> 5;
-    int aoff[4], boff[2][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        aoff[i] = i8_rl_off(wm * 32 + lr, 2 * i + lh);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) boff[nt][i] = NCH * T::CHB + i8_rl_off(wn * 64 + nt * 32 + lr, 2 * i + lh);
-    }
-
-    const int8_t *gb_cur = nullptr, *gb_nxt = nullptr;
-    const int *es_cur[NEP] = {}, *es_nxt[NEP] = {};
-    if (ntile_wg > 0) {
-        tile_base(0, gb_cur, es_cur);
-        if (wave == 0) issue_exp(es_cur, 0);
-        for (int k = 0; k < PD && k < NK; ++k) issue(gb_cur, k, k % NBUF, 0, GL);
-    }
-    int s = 0, bcur = 0, bpre = PD % NBUF;  // ring buffers of stage s and of stage s + PD
-    float4 pend[2][4];  // DEFER: the previous tile's M rows
-    float* prow[2] = {nullptr, nullptr};
-    auto store_pend = [&]() {
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) *(float4*)(prow[nt] + 8 * k) = pend[nt][k];
-    };
-    for (int n = 0; n < ntile_wg; ++n) {
-        if (n + 1 < ntile_wg) tile_base(n + 1, gb_nxt, es_nxt);
-        i32x16_t acc[4][2];
-#pragma unroll
-        for (int l = 0; l < 4; ++l)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) acc[l][nt] = i32x16_t{};
-        int evr[NSEG][2];  // ev - 35 of the wave's two 32-board blocks (this lane's board), per segment
-        int euv[4][4];     // eu of this lane's 16 output channels
-        double sacc[NSEG == 2 ? 2 : 1][NSEG == 2 ? 16 : 1];  // segment 0, scaled (NSEG 2)
-        for (int kt = 0; kt < NK; ++kt, ++s, bcur = bcur + 1 == NBUF ? 0 : bcur + 1,
-                                     bpre = bpre + 1 == NBUF ? 0 : bpre + 1) {
-            // stage s has landed once only the batches issued after it may be outstanding: the next PD - 1
-            // stages' (those that exist) and, in a tile's first PD stages after an epilogue, its NS stores
-            const int ahead = nstage - 1 - s < PD - 1 ? nstage - 1 - s : PD - 1;
-            const bool st = DEFER ? (n > 0 && kt >= 1 && kt <= PD) : (n > 0 && kt < PD);
-            if (PD == 2) {
-                if (ahead == 1) {
-                    if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL + T::NS) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL) : "memory");
-                } else {
-                    if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(T::NS) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-            } else {  // PD == 3
-                if (ahead == 2) {
-                    if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GL + T::NS) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GL) : "memory");
-                } else if (ahead == 1) {
-                    if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL + T::NS) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL) : "memory");
-                } else {
-                    if (st) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(T::NS) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-            }
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (kt == 0) {  // the tile's exponents landed with its first stage: ev of the 2 boards, eu of 16 channels
-                const int* ex = (const int*)(L0 + T::EXP + (n & 1) * 2048);
-#pragma unroll
-                for (int sg = 0; sg < NSEG; ++sg)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) evr[sg][nt] = ex[sg * 128 + wn * 64 + nt * 32 + lr] - 35;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) euv[k][jj] = ex[NSEG * 128 + wm * 32 + 8 * k + 4 * lh + jj];
-            }
-            const char* buf = L0 + bcur * T::STAGE;
-            const bool more = s + PD < nstage;
-#pragma unroll
-            for (int ch = 0; ch < NCH; ++ch) {
-                const char* cb = buf + ch * T::CHB;
-                i8x16_t a[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a[i] = *(const i8x16_t*)(cb + aoff[i]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    i8x16_t b[2];
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) b[nt] = *(const i8x16_t*)(cb + boff[nt][j]);
-#pragma unroll
-                    for (int i = 0; i + j < 4; ++i)
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
-                            acc[i + j][nt] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[i], b[nt], acc[i + j][nt], 0, 0, 0);
-                    // stage s + PD's copies (this tile's or the next one's), one group per (chunk, B digit)
-                    // between the MFMA groups; the next tile's exponents ahead of its first stage
-                    if (more) {
-                        constexpr int PER = GL / (4 * NCH);
-                        const int g0 = (ch * 4 + j) * PER;
-                        const bool nx = kt + PD >= NK;
-                        if (nx && kt + PD == NK && g0 == 0 && wave == 0) issue_exp(es_nxt, n + 1);
-                        issue(nx ? gb_nxt : gb_cur, nx ? kt + PD - NK : kt + PD, bpre, g0, g0 + PER);
-                    }
-                }
-            }
-            if (DEFER && kt == 0 && n > 0) store_pend();  // after this stage's copies (stage s + PD's)
-            if constexpr (NSEG == 2) {
-              if (kt == NK / 2 - 1) {  // segment 0 done: its exact value, scaled, then restart
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    const double sc = ldexp(1.0, evr[0][nt]);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int hi = acc[0][nt][r] * 128 + acc[1][nt][r];
-                        const int lo = acc[2][nt][r] * 128 + acc[3][nt][r];
-                        sacc[nt][r] = __builtin_fma((double)hi, 16384.0, (double)lo) * sc;  // exact
-                    }
-#pragma unroll
-                    for (int l = 0; l < 4; ++l) acc[l][nt] = i32x16_t{};
-                }
-              }
-            }
-        }
-        // epilogue (registers only; the ring keeps loading the next tile)
-        int xi, n_base, r_base;
-        tile_of(n, xi, n_base, r_base);
-        gb_cur = gb_nxt;
-#pragma unroll
-        for (int p = 0; p < NEP; ++p) es_cur[p] = es_nxt[p];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-            const int bl = wn * 64 + nt * 32 + lr;
-            const int eb = evr[NSEG - 1][nt];
-            const double sc1 = ldexp(1.0, eb);
-            float* mrow = M + ((size_t)xi * stride + r_base + bl) * 512 + n_base + wm * 32 + 4 * lh;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                float o[4];
-                const int* ec = euv[k];
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    const int r = 4 * k + jj;
-                    const int hi = acc[0][nt][r] * 128 + acc[1][nt][r];
-                    const int lo = acc[2][nt][r] * 128 + acc[3][nt][r];
-                    const double m = __builtin_fma((double)hi, 16384.0, (double)lo);  // exact
-                    if constexpr (NSEG == 2)  // segment 1 scaled (exact) plus segment 0: one fp64 rounding
-                        o[jj] = (float)ldexp(__builtin_fma(m, sc1, sacc[nt][r]), ec[jj]);
-                    else
-                        o[jj] = (float)ldexp(m, eb + ec[jj]);
-                }
-                if (ABL == 1)
-                    asm volatile("" ::"v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]));
-                else if (DEFER)
-                    pend[nt][k] = make_float4(o[0], o[1], o[2], o[3]);
-                else
-                    *(float4*)(mrow + 8 * k) = make_float4(o[0], o[1], o[2], o[3]);
-            }
-            if (DEFER) prow[nt] = mrow;
-        }
-    }
-    if (DEFER && ntile_wg > 0) store_pend();
-}
-
 // ---- the fp32 Winograd domain with int8-digit GEMMs (KV_PATH_WINO88_I8F32) ----
 // The fp32 F(8x8) tower's arithmetic (kv_wino88.h: fp32 transforms, V, M and activations; U as
 // 4 digits of the fp64 U) with each GEMM taken from 4 int8 digits per value: per-row 28-bit block
@@ -1925,36 +1319,6 @@ __global__ __launch_bounds__(512) void wino88i32_gemm_kernel(const int8_t* __res
 // workgroup per CU, 436-511 us per layer against 142-238 + 165 us for the out kernel + slice,
 // profiles/r04_i8f32_fused_out.log; and an output kernel computing only the row maxima plus a second
 // input-transform pass, 294-356 + 220 us, profiles/r04_i8f32_outmax_form.log.)
-
-// fp32 transform row 5h + aa of a plane split over lanes l, l ^ 32 (half h), from the half's 4 columns after the
-// half exchange (xc[kk][i] = pixel (i, 4h + kk)): the fmaf chains of wino88_input_cols + wino88_input_row on the
-// same inputs -- each column's w88_bt taken for rows aa and 5 + aa only -- so the same bits, and no 10x4
-// intermediate is live. The asm makes xc opaque per row: otherwise the compiler merges the two passes of
-// wino88i32_out2_kernel (the same chains on the same values) and keeps the 50 results across the barrier.
-__device__ inline void wino88_input_row_of_cols(float (&xc)[4][8], int aa, float (&o)[10]) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(xc[kk][i]));
-    float row[10];
-    row[0] = 0.f;
-    row[9] = 0.f;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-        float col[10], t[10];
-        col[0] = 0.f;
-        col[9] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) col[1 + i] = xc[kk][i];
-        w88_bt(col, t);
-        float lo = t[aa], hi = t[5 + aa];
-        half_swap(lo, hi);
-        row[1 + kk] = lo;
-        row[5 + kk] = hi;
-    }
-    w88_bt(row, o);
-}
 
 // Row-line width: 4 digit slots (128 bytes) per 32-channel chunk, or R3's 3 (96 bytes: no zero slot in memory)
 template <bool R3>
@@ -1984,99 +1348,6 @@ __device__ inline unsigned i8f32_digits(float v, int e) {
         return i8_digits4_packed(v, e);
 }
 
-// Phase stagger of the one-board-per-workgroup output kernels: every board runs load M -> transforms -> store
-// digits, and boards that start together on every CU put the whole chip in the same phase (HBM saturated in the
-// load and store phases, idle in the transforms). The first-round workgroups of half the CUs (first: the
-// resident workgroup count; (b >> 3) & 1 picks half the workgroups of each XCD) wait `stag` x 8,128 cycles
-// before starting, and the slots they occupy keep that offset for the rest of the grid. Timing only: no
-// output depends on it.
-__device__ inline void out_stagger(int b, int stag, int first) {
-    if (b < first && ((b >> 3) & 1))
-        for (int i = 0; i < stag; ++i) __builtin_amdgcn_s_sleep(127);
-}
-
-// wino88i32_out2_kernel: wino88i32_out_kernel<RESID, WRITE_Y, 512>'s result, bit for bit, in a register budget
-// that lets two boards (two 1,024-thread workgroups) share a CU, so one board's digit stores drain under the
-// other's transforms: a lane keeps its 32 fp32 activations (xc) across the exponent barrier instead of 50 V
-// values and runs the input transform twice -- once for the row maxima, once for the digits. The transform is
-// partitioned by row, not repeated within a pass (each pass computes each V value once), so the VALU work is
-// twice the held form's input transform; at 8 waves per SIMD that is ~20 us of issue over 2,048 boards.
-template <bool RESID, bool WRITE_Y, bool R3 = false>
-__global__ __launch_bounds__(1024, 8) void wino88i32_out2_kernel(const float* __restrict__ M, int rows,
-                                                                 const float* __restrict__ scale,
-                                                                 const float* __restrict__ shift, const float* resid,
-                                                                 float* Y, int8_t* __restrict__ V8,
-                                                                 int* __restrict__ ex, int stag, int first) {
-#pragma clang fp contract(off)
-    constexpr int NK = 512 / 32, NW = 16;
-    __shared__ __attribute__((aligned(16))) unsigned red[NW][2][5][16];
-    __shared__ int exs[100];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5;
-    const int c = w * 32 + (lane & 31), b = out_board<R3>((int)blockIdx.y);
-    out_stagger(b, stag, first);
-    float xc[4][8];  // the half's columns 4h .. 4h+3, all 8 rows (after the half exchange)
-    {
-        float x2[4][8];
-        wino88_out_plane_half<RESID, WRITE_Y, true>(M, rows, b, c, h, scale[c], shift[c], resid, Y, x2);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-                float lo = x2[ii][kk], hi = x2[ii][4 + kk];
-                half_swap(lo, hi);
-                xc[kk][ii] = lo;
-                xc[kk][4 + ii] = hi;
-            }
-    }
-#pragma unroll
-    for (int aa = 0; aa < 5; ++aa) {
-        float o[10];
-        wino88_input_row_of_cols(xc, aa, o);
-        unsigned m[10];
-#pragma unroll
-        for (int bb = 0; bb < 10; ++bb) m[bb] = i8_half_max_dpp(__float_as_uint(o[bb]) & 0x7fffffffu);
-        if ((lane & 31) == 16) {  // this half's 10 maxima, written by one lane
-            uint4* rr = (uint4*)&red[w][h][aa][0];
-            rr[0] = make_uint4(m[0], m[1], m[2], m[3]);
-            rr[1] = make_uint4(m[4], m[5], m[6], m[7]);
-            *(uint2*)&red[w][h][aa][8] = make_uint2(m[8], m[9]);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 100) {
-        const int xi = threadIdx.x, a = xi / 10, bb = xi % 10, hh = a / 5, aa = a % 5;
-        unsigned m = 0;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) m = red[ww][hh][aa][bb] > m ? red[ww][hh][aa][bb] : m;
-        const int e = i8f32_row_exponent<R3>(m);
-        exs[xi] = e;
-        ex[(size_t)xi * rows + b] = e;
-    }
-    __syncthreads();
-    const int q = lane & 3;
-    const unsigned off0 = ((unsigned)(c >> 5) * rows + b) * kI8LineBytes<R3> + q * 32 + (c & 28),
-                   xstride = NK * rows * kI8LineBytes<R3>;
-    unsigned* const dst = (unsigned*)V8;
-#pragma unroll
-    for (int aa = 0; aa < 5; ++aa) {
-        float o[10];
-        wino88_input_row_of_cols(xc, aa, o);
-        const int a = 5 * h + aa;
-#pragma unroll
-        for (int bb = 0; bb < 10; ++bb) {
-            const int xi = a * 10 + bb;
-            const unsigned P = i8f32_digits<R3>(o[bb], exs[xi]);
-            {
-                const unsigned T4 = i8_quad_transpose(P, lane);  // lane q of the quad: digit q's 4 channels
-                if constexpr (!R3)
-                    __builtin_nontemporal_store(T4, &dst[(off0 + (unsigned)xi * xstride) >> 2]);
-                else if (q < 3)  // R3's 96-byte lines share 128-byte lines: ordinary stores, merged in L2
-                    dst[(off0 + (unsigned)xi * xstride) >> 2] = T4;
-            }
-        }
-    }
-}
-
 // STAMP (a diagnostic build, never the product's; kv_dev_out_phases): waves 0 and 15 record the shader clock at the
 // kernel's phase boundaries into kOutStamps[board][wave 0/15][8] -- a buffer no other code reads: start, V ready
 // (M loaded, both transforms done), after the maxima barrier, after the exponent barrier, digit stores issued,
@@ -2084,20 +1355,23 @@ __global__ __launch_bounds__(1024, 8) void wino88i32_out2_kernel(const float* __
 constexpr int kOutStampBoards = 4096;
 __device__ unsigned long long kOutStamps[kOutStampBoards][2][8];
 
-template <bool RESID, bool WRITE_Y, int CW, bool R3 = false, bool STAMP = false, int ABL = 0, bool YNT = false>
+// CW channels per workgroup (2 CW threads: a plane split over lanes l, l ^ 32): 512 only -- the row's exponent
+// over all its channels, one workgroup per board, grid (1, boards), so blockIdx.x is 0. (The CW 256 form, an
+// exponent per 256-channel segment from two workgroups per board, was built, measured and removed; the callers'
+// exponent buffers hold one exponent per row and would not take it.)
+template <bool RESID, bool WRITE_Y, int CW, bool R3 = false, bool STAMP = false, bool YNT = false>
 __global__ __launch_bounds__(2 * CW) void wino88i32_out_kernel(const float* __restrict__ M, int rows,
                                                                const float* __restrict__ scale,
                                                                const float* __restrict__ shift, const float* resid,
                                                                float* Y, int8_t* __restrict__ V8,
-                                                               int* __restrict__ ex, int stag, int first) {
+                                                               int* __restrict__ ex) {
 #pragma clang fp contract(off)
-    static_assert(CW == 512 || CW == 256, "a row or a 256-channel segment per workgroup");
+    static_assert(CW == 512, "a row per workgroup (the exponent buffers hold one exponent per row)");
     constexpr int NK = 512 / 32, NW = CW / 32, NSEG = 512 / CW;
     __shared__ __attribute__((aligned(16))) unsigned red[NW][2][5][16];
     __shared__ int exs[100];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5;
     const int seg = blockIdx.x, c = seg * CW + w * 32 + (lane & 31), b = out_board<R3>((int)blockIdx.y);
-    out_stagger(b, stag, first);
     unsigned long long st[6] = {};
     const bool stamper = STAMP && (w == 0 || w == NW - 1) && lane == 0 && b < kOutStampBoards;
     if constexpr (STAMP) st[0] = __builtin_amdgcn_s_memtime();
@@ -2106,7 +1380,7 @@ __global__ __launch_bounds__(2 * CW) void wino88i32_out_kernel(const float* __re
         float t2[10][4];  // B10^T of the plane's columns 4h .. 4h+3
         {
             float x2[4][8];
-            wino88_out_plane_half<RESID, WRITE_Y, false, ABL, YNT>(M, rows, b, c, h, scale[c], shift[c], resid, Y, x2);
+            wino88_out_plane_half<RESID, WRITE_Y, YNT>(M, rows, b, c, h, scale[c], shift[c], resid, Y, x2);
             wino88_input_cols(x2, h, t2);
         }
 #pragma unroll
@@ -2286,171 +1560,6 @@ __global__ __launch_bounds__(512) void stem_r3_kernel(const int8_t* __restrict__
     }
 }
 
-// wino88i32_outp_kernel: wino88i32_out_kernel<RESID, WRITE_Y, 512, R3>'s result, bit for bit, as a persistent
-// kernel that streams M through LDS by DMA. One 1,024-thread workgroup per CU loops over its boards (blockIdx.x,
-// + gridDim.x, ...); a board's output transform runs in 5 column steps, step jj reading M's points i*10 + jj and
-// i*10 + 5 + jj (the two plane halves' columns, 20 points x 512 channels = 40 KiB: a "slot"). Slots are copied
-// global -> LDS by global_load_lds_dwordx4 (1 KiB per wave-instruction, 40 per slot, dealt over the 16 waves)
-// into a ring of 3 LDS buffers, two steps ahead -- across the board boundary, so the next board's first two
-// slots land while this board reduces its row maxima and stores its digits. The M loads then hold no VGPRs (the
-// held kernel keeps 50 loads per lane in flight at the board's start, the 64-register one only 10), and a board's
-// load latency hides under its predecessor's back half. Same fmaf chains on the same values as the held kernel.
-// Waits: before step t the wave waits for its own pieces of slot t (vmcnt = its pieces of slot t + 1, the only
-// VMEM issued since) and lgkmcnt(0) (its reads of slot t - 1, whose buffer slot t + 2's copies overwrite once
-// every wave passes this barrier); the first two slots of a later board were drained by the vmcnt(0) before the
-// previous board's digit stores.
-template <bool RESID, bool WRITE_Y, bool R3 = false>
-__global__ __launch_bounds__(1024) void wino88i32_outp_kernel(const float* __restrict__ M, int rows,
-                                                              const float* __restrict__ scale,
-                                                              const float* __restrict__ shift, const float* resid,
-                                                              float* Y, int8_t* __restrict__ V8,
-                                                              int* __restrict__ ex) {
-#pragma clang fp contract(off)
-    constexpr int NK = 512 / 32, NW = 16, NSLOT = 3, SLOT = 20 * 2048;
-    extern __shared__ __attribute__((aligned(16))) char lds_outp[];  // NSLOT slots, then red, exs
-    unsigned(*red)[2][5][16] = (unsigned(*)[2][5][16])(lds_outp + NSLOT * SLOT);
-    int* exs = (int*)(lds_outp + NSLOT * SLOT + NW * 2 * 5 * 16 * 4);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5;
-    const int wu = __builtin_amdgcn_readfirstlane(w);
-    const int c = w * 32 + (lane & 31);
-    const int G = (int)gridDim.x;
-    const int nbw = ((int)rows - (int)blockIdx.x + G - 1) / G;  // boards of this workgroup
-    const int nsteps = 5 * nbw;
-    const int npieces = wu < 8 ? 3 : 2;  // this wave's pieces of a slot (40 = 16 + 16 + 8)
-    const float sc = scale[c], sh = shift[c];
-    const unsigned xs = (unsigned)rows * 512;
-    // slot of step t: board blockIdx.x + (t / 5) G, column step t % 5; LDS row r = hh * 10 + i holds point
-    // i * 10 + 5 hh + jj; piece q = row q / 2, channels 256 (q & 1) ..
-    auto issue = [&](int t) {
-        if (t >= nsteps) return;
-        const int b = (int)blockIdx.x + (t / 5) * G, jj = t % 5;
-        char* dst = lds_outp + (t % NSLOT) * SLOT;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const int q = wu + 16 * k;
-            if (q < 40) {
-                const int r = q >> 1, hh = r / 10, i = r - 10 * hh;
-                const float* src = M + (unsigned)(i * 10 + 5 * hh + jj) * xs + (unsigned)b * 512 + (q & 1) * 256 +
-                                   lane * 4;
-                __builtin_amdgcn_global_load_lds((const void*)src,
-                                                 (__attribute__((address_space(3))) void*)(dst + q * 1024), 16, 0, 0);
-            }
-        }
-    };
-    issue(0);
-    issue(1);
-    int t = 0;
-    for (int k = 0; k < nbw; ++k) {
-        const int b = (int)blockIdx.x + k * G;
-        float tt[8][5];  // A8^T m of this half's columns 5h + jj
-#pragma unroll
-        for (int jj = 0; jj < 5; ++jj, ++t) {
-            if (k > 0 && jj < 2) {  // drained before the previous board's digit stores
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            } else {
-                const int younger = t + 1 < nsteps ? npieces : 0;  // slot t + 1's pieces, issued after slot t's
-                if (younger == 3)
-                    asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
-                else if (younger == 2)
-                    asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-                else
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            }
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            issue(t + 2);  // into slot t - 1's buffer: every wave has read it (lgkmcnt(0) before this barrier)
-            const float* sl = (const float*)(lds_outp + (t % NSLOT) * SLOT) + h * 10 * 512 + c;
-            float col[10], o[8];
-#pragma unroll
-            for (int i = 0; i < 10; ++i) col[i] = sl[i * 512];
-            w88_at(col, o);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) tt[i][jj] = o[i];
-        }
-        // the row pass, BN (+ residual) + ReLU (+ Y) -- wino88_out_plane_half's
-        float x2[4][8];
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-            float row[10];
-#pragma unroll
-            for (int jj = 0; jj < 5; ++jj) {
-                float lo = tt[ii][jj], hi = tt[4 + ii][jj];
-                half_swap(lo, hi);
-                row[jj] = lo;
-                row[5 + jj] = hi;
-            }
-            float o[8];
-            w88_at(row, o);
-            const int i = 4 * h + ii;
-            float res[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) res[j] = RESID ? resid[((unsigned)b * 64 + i * 8 + j) * 512 + c] : 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float v = o[j] * sc + sh;
-                if (RESID) v += res[j];
-                v = v > 0.f ? v : 0.f;
-                if (WRITE_Y) Y[((unsigned)b * 64 + i * 8 + j) * 512 + c] = v;
-                x2[ii][j] = v;
-            }
-        }
-        // the next V (held: 50 values per lane), its row maxima, exponents, digits -- wino88i32_out_kernel's
-        float vk[5][10];
-        {
-            float t2[10][4];
-            wino88_input_cols(x2, h, t2);
-#pragma unroll
-            for (int aa = 0; aa < 5; ++aa) wino88_input_row(t2, h, aa, vk[aa]);
-        }
-#pragma unroll
-        for (int aa = 0; aa < 5; ++aa) {
-            unsigned m[10];
-#pragma unroll
-            for (int bb = 0; bb < 10; ++bb) m[bb] = i8_half_max_dpp(__float_as_uint(vk[aa][bb]) & 0x7fffffffu);
-            if ((lane & 31) == 16) {
-                uint4* rr = (uint4*)&red[w][h][aa][0];
-                rr[0] = make_uint4(m[0], m[1], m[2], m[3]);
-                rr[1] = make_uint4(m[4], m[5], m[6], m[7]);
-                *(uint2*)&red[w][h][aa][8] = make_uint2(m[8], m[9]);
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x < 100) {
-            const int xi = threadIdx.x, a = xi / 10, bb = xi % 10, hh = a / 5, aa = a % 5;
-            unsigned m = 0;
-#pragma unroll
-            for (int ww = 0; ww < NW; ++ww) m = red[ww][hh][aa][bb] > m ? red[ww][hh][aa][bb] : m;
-            const int e = i8f32_row_exponent<R3>(m);
-            exs[xi] = e;
-            ex[(size_t)xi * rows + b] = e;
-        }
-        __syncthreads();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next board's first two slots (and Y) landed
-        const int q = lane & 3;
-        const unsigned off0 = ((unsigned)(c >> 5) * rows + b) * kI8LineBytes<R3> + q * 32 + (c & 28),
-                   xstride = NK * rows * kI8LineBytes<R3>;
-        unsigned* const dst = (unsigned*)V8;
-#pragma unroll
-        for (int aa = 0; aa < 5; ++aa) {
-            const int a = 5 * h + aa;
-#pragma unroll
-            for (int bb = 0; bb < 10; ++bb) {
-                const int xi = a * 10 + bb;
-                const unsigned P = i8f32_digits<R3>(vk[aa][bb], exs[xi]);
-                {
-                const unsigned T4 = i8_quad_transpose(P, lane);  // lane q of the quad: digit q's 4 channels
-                if constexpr (!R3)
-                    __builtin_nontemporal_store(T4, &dst[(off0 + (unsigned)xi * xstride) >> 2]);
-                else if (q < 3)  // R3's 96-byte lines share 128-byte lines: ordinary stores, merged in L2
-                    dst[(off0 + (unsigned)xi * xstride) >> 2] = T4;
-            }
-            }
-        }
-    }
-}
-
-constexpr int kOutpLds = 3 * 20 * 2048 + 16 * 2 * 5 * 16 * 4 + 100 * 4;  // wino88i32_outp_kernel's dynamic LDS
-
 // ---- the fp32 tower with fp64 input transforms (KV_PATH_WINO88_I8F32V) ----
 // The same tower as KV_PATH_WINO88_I8F32 (fp32 M, output transform and activations, the 4-digit GEMM)
 // except that every conv's V is the fp64 input transform of its fp32 input, cut to 4 digits from fp64:
@@ -2504,14 +1613,13 @@ __device__ inline void wino88d_input_row_of_cols(float (&xc)[4][8], int aa, doub
 template <bool RESID, bool WRITE_Y, class MT>
 __device__ inline void wino88v_out_body(const MT* __restrict__ M, int rows, const float* __restrict__ scale,
                                         const float* __restrict__ shift, const float* resid, float* Y,
-                                        int8_t* __restrict__ V8, int* __restrict__ ex, int stag, int first) {
+                                        int8_t* __restrict__ V8, int* __restrict__ ex) {
     constexpr bool R8 = sizeof(MT) == 8;
     constexpr int NK = 512 / 32, NW = 16;
     __shared__ __attribute__((aligned(16))) unsigned red[NW][2][5][16];
     __shared__ int exs[100];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5;
     const int c = w * 32 + (lane & 31), b = blockIdx.y;
-    out_stagger(b, stag, first);
     float xc[4][8];  // the half's columns 4h .. 4h+3, all 8 rows (after the half exchange)
     {
         float x2[4][8];
@@ -2584,18 +1692,16 @@ template <bool RESID, bool WRITE_Y>
 __global__ __launch_bounds__(1024) void wino88i32v_out_kernel(const float* __restrict__ M, int rows,
                                                               const float* __restrict__ scale,
                                                               const float* __restrict__ shift, const float* resid,
-                                                              float* Y, int8_t* __restrict__ V8, int* __restrict__ ex,
-                                                              int stag, int first) {
-    wino88v_out_body<RESID, WRITE_Y>(M, rows, scale, shift, resid, Y, V8, ex, stag, first);
+                                                              float* Y, int8_t* __restrict__ V8, int* __restrict__ ex) {
+    wino88v_out_body<RESID, WRITE_Y>(M, rows, scale, shift, resid, Y, V8, ex);
 }
 
 template <bool RESID, bool WRITE_Y>
 __global__ __launch_bounds__(1024) void wino88i64r_out_kernel(const double* __restrict__ M, int rows,
                                                               const float* __restrict__ scale,
                                                               const float* __restrict__ shift, const float* resid,
-                                                              float* Y, int8_t* __restrict__ V8, int* __restrict__ ex,
-                                                              int stag, int first) {
-    wino88v_out_body<RESID, WRITE_Y>(M, rows, scale, shift, resid, Y, V8, ex, stag, first);
+                                                              float* Y, int8_t* __restrict__ V8, int* __restrict__ ex) {
+    wino88v_out_body<RESID, WRITE_Y>(M, rows, scale, shift, resid, Y, V8, ex);
 }
 
 }  // namespace kv

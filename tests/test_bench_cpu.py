@@ -54,8 +54,8 @@ def test_gemm_traffic_summary_present():
     (6, "wino88i32_gemm_lagt_kernel<512,4>", 4), (7, "wino88i32_gemm_lagt_kernel<512,5>", 5),
     (9, "wino88i32_gemm_r3k64_kernel<512,5>", 5), (9, "wino88i32_gemm_r3k64_kernel<512,4>", 4),
     (9, "wino88i32_gemm_lagt_kernel<512,5,3>", 5),
-    # KV_I8F32_TPW=1 (or a CU count where multi-tile workgroups do not pay): the library reports the
-    # single-tile kernel, and the line follows it
+    # a CU count where multi-tile workgroups do not pay: the library reports the single-tile kernel, and the
+    # line follows it
     (6, "wino88i32_gemm_lag_kernel<512,false>", 1)])
 def test_gemm_label_is_the_librarys(path, kernel, tpw):
     """bench.py labels the dominant GEMM with the name the library reports for the launch it made

@@ -1,8 +1,7 @@
 """Back-to-back time of the headline GEMM at ROWS boards (kv_dev_gemm_clock: the product's fp32-tower GEMM on
-seeded random digits for SECONDS, then one stamped launch for the clock). The kernel form follows the
-environment (KV_I8R3_K64, KV_R3K64_ABL ...): one line per call.
+seeded random digits for SECONDS, then one stamped launch for the clock): one line per call.
 
-    KV_I8R3_K64=1 python tools/gemm_b2b.py TAG [ROWS] [DIGITS] [SECONDS]
+    python tools/gemm_b2b.py TAG [ROWS] [DIGITS] [SECONDS]
 """
 import ctypes as C
 import os

@@ -1,4 +1,4 @@
-"""F(8x8) vs F(4x8) on one GPU: forward time (alternating, HIP events) at
+"""F(8x8) in fp32 vs the R3 int8-digit tower on one GPU: forward time (alternating, HIP events) at
 256 / 1,024 / 2,048 boards and max |dlogit| / |dvalue| against the float64
 restatement on the peaked and bn weights (KV_PROBE_BOARDS random boards, 64).
 
@@ -31,12 +31,12 @@ def main():
     for variant in ("peaked", "bn"):
         sd64 = {k: torch.from_numpy(np.asarray(v, dtype=np.float64)) for k, v in synthetic_state_dict(42, variant).items()}
         rp, rv = torch_ref.forward(sd64, torch.from_numpy(planes.astype(np.float64)))
-        for algo in ("winograd48", "winograd88"):
+        for algo in ("winograd88", "winograd88i8r3"):
             p, v = net(variant, algo)(torch.from_numpy(planes).cuda())
             dp = np.abs(p.cpu().numpy().astype(np.float64) - rp.numpy()).max()
             dv = np.abs(v.cpu().numpy().astype(np.float64) - rv.numpy()).max()
             print(f"{variant} {algo}: max |dlogit| {dp:.3e} max |dvalue| {dv:.3e}", flush=True)
-    nets = {a: net("bn", a).kv_net(0) for a in ("winograd48", "winograd88")}
+    nets = {a: net("bn", a).kv_net(0) for a in ("winograd88", "winograd88i8r3")}
     for B in (256, 1024, 2048):
         codes = torch.randint(0, 13, (B, 64), dtype=torch.int8, device="cuda")
         res = {a: [] for a in nets}

@@ -203,6 +203,16 @@ typedef struct {
     int algo;             /* KV_ALGO_* of the network convs */
     int tree_edge_cap;    /* MCTS edges per slot; <= 0: KV_MAXM x (sims + 1), which cannot overflow. An
                              expansion that does not fit raises KV_EOVERFLOW (kv_stats.tree_overflows) */
+    float forced_k;       /* Forced playouts and policy target pruning (MCTS self-play, DESIGN.md "Forced playouts and
+                             policy target pruning"). 0: off (no kernel takes another path, no byte changes). Else
+                             0 < forced_k <= 16 (KataGo: 2): on a full ply a root edge with n > 0 visits is taken
+                             before any PUCT score while n * n < forced_k * P * S (S the root's visit sum); at the move
+                             choice the forced visits PUCT would not have made are taken out again, the move is drawn
+                             from the pruned counts T (sample_plies: their first maximum), and T is kept beside the
+                             raw counts for kv_root_targets[_device] when keep_root_visits is set. kv_root_visits, the
+                             carried subtree and every counter keep the raw counts; a fast ply (fast_sims) has no
+                             forcing and T = N. Needs sims >= 1 and arena 0; negative, non-finite or above 16:
+                             KV_EINVAL. (forced_k stands before keep_root_visits) */
     int keep_root_visits; /* 1: keep each MCTS move's root visit counts (pi) for kv_root_visits[_device];
                              2: as 1, and also each committed move's root move words for kv_root_moves[_device] */
     int fast_sims;        /* Playout cap randomization (MCTS self-play, DESIGN.md "Playout cap randomization"). 0: off,
@@ -324,7 +334,12 @@ typedef struct {
                                (the rest as 64x128 tiles in a second one; 100: one launch); 0 otherwise */
     char dom_kernel[96];    /* the name of the kernel those launches ran, as the library chose it (template
                                arguments included, e.g. "wino88i32_gemm_lagt_kernel<512,5>") */
-    int64_t plies_full;     /* committed plies searched to cfg.sims (== plies with kv_config.fast_sims 0) and */
+    int64_t forced_descents; /* kv_config.forced_k: descents at whose root an edge was under its forced count, so
+                               that the forced rule and not PUCT chose the root edge, and */
+    int64_t visits_pruned;  /* the root visits the pruning took out of the policy targets, the sum over the committed
+                               plies of (the raw counts' sum - the pruned counts' sum). Both counted at the move
+                               choice; 0 with forced_k 0. (The two stand before plies_full) */
+    int64_t plies_full;    /* committed plies searched to cfg.sims (== plies with kv_config.fast_sims 0) and */
     int64_t plies_fast;     /* to cfg.fast_sims, counted at the move choice. reuse_tree 0: sims == plies_full x
                                cfg.sims + plies_fast x cfg.fast_sims; reuse_tree 1: sims + sims_kept == the sum of
                                the committed plies' root visit sums, each max(the ply's target, the visits carried
@@ -405,6 +420,14 @@ int kv_root_moves(kv_engine* e, uint16_t* out, size_t cap, size_t* n);
 /* the same words device to device in the engine's record order (row k belongs to record k of kv_records_device
  * and row k of kv_root_visits_device); stream as in kv_records_device */
 int kv_root_moves_device(kv_engine* e, uint16_t* out_dev, size_t cap, size_t* n, void* stream);
+/* The pruned root counts T of every committed move (kv_config.forced_k > 0 with keep_root_visits set; DESIGN.md
+ * "Forced playouts and policy target pruning"): the policy target, kv_root_visits' layout, order and padding -- out
+ * [n][KV_MAXM], -1 padded, rows in kv_records' order. A fast ply's row is its raw counts. On an engine created with
+ * forced_k 0 or keep_root_visits 0: KV_EINVAL. */
+int kv_root_targets(kv_engine* e, int32_t* out, size_t cap, size_t* n);
+/* the same counts device to device, kv_root_visits_device's layout (uint16, 0xffff padded, the engine's record
+ * order); stream as in kv_records_device */
+int kv_root_targets_device(kv_engine* e, uint16_t* out_dev, size_t cap, size_t* n, void* stream);
 int kv_sync(kv_engine* e);
 void kv_destroy(kv_engine* e);
 

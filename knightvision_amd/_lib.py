@@ -21,7 +21,7 @@ class Config(C.Structure):
                 ("max_moves", C.c_int), ("batch", C.c_int), ("eps", C.c_double), ("alpha", C.c_double),
                 ("sims", C.c_int), ("c_puct", C.c_float), ("eval_mode", C.c_int), ("record_cap", C.c_int64),
                 ("recycle", C.c_int), ("precision", C.c_int), ("algo", C.c_int), ("tree_edge_cap", C.c_int),
-                ("keep_root_visits", C.c_int), ("fast_sims", C.c_int), ("full_q16", C.c_int), ("eval_cache", C.c_int), ("leaves", C.c_int), ("arena", C.c_int), ("sample_plies", C.c_int),
+                ("forced_k", C.c_float), ("keep_root_visits", C.c_int), ("fast_sims", C.c_int), ("full_q16", C.c_int), ("eval_cache", C.c_int), ("leaves", C.c_int), ("arena", C.c_int), ("sample_plies", C.c_int),
                 ("sim_groups", C.c_int), ("reuse_tree", C.c_int)]
 
 
@@ -41,6 +41,7 @@ class Stats(C.Structure):
                 ("res_conv_launches", C.c_int64), ("step_ms", C.c_double), ("dom_flop", C.c_double),
                 ("dom_algo", C.c_int64), ("tree_overflows", C.c_int64), ("nn_rows_lazy", C.c_int64),
                 ("dom_path", C.c_int64), ("dom_split", C.c_int64), ("dom_kernel", C.c_char * 96),
+                ("forced_descents", C.c_int64), ("visits_pruned", C.c_int64),
                 ("plies_full", C.c_int64), ("plies_fast", C.c_int64),
                 ("arena_rows", C.c_int64 * 2), ("cache_probes", C.c_int64), ("cache_hits", C.c_int64),
                 ("cache_stores", C.c_int64), ("sim_steps", C.c_int64), ("leaf_rows_pending", C.c_int64),
@@ -134,6 +135,8 @@ def _declare(L):
         "kv_root_visits_device": ([vp, vp, sz, P(sz), vp], i),
         "kv_root_moves": ([vp, P(C.c_uint16), sz, P(sz)], i),
         "kv_root_moves_device": ([vp, vp, sz, P(sz), vp], i),
+        "kv_root_targets": ([vp, P(C.c_int32), sz, P(sz)], i),
+        "kv_root_targets_device": ([vp, vp, sz, P(sz), vp], i),
         "kv_records_device": ([vp, vp, sz, P(sz), vp], i),
         "kv_sync": ([vp], i),
         "kv_reset_records": ([vp], i),
@@ -203,7 +206,7 @@ EXPORTED = ["kv_last_error", "kv_version", "kv_net_packed_size", "kv_net_create"
             "kv_net_forward_boards", "kv_net_forward_boards_legal", "kv_net_set_timing", "kv_net_last_timing", "kv_net_destroy", "kv_net_set_precision", "kv_net_set_algo",
             "kv_net_calibration", "kv_engine_calibration",
             "kv_create", "kv_sim_groups_for",
-            "kv_load_weights", "kv_load_weights_b", "kv_engine_calibration_b", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_sizeof_config", "kv_sizeof_stats", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
+            "kv_load_weights", "kv_load_weights_b", "kv_engine_calibration_b", "kv_run", "kv_set_max_moves", "kv_records", "kv_games", "kv_stats_get", "kv_sizeof_config", "kv_sizeof_stats", "kv_root_visits", "kv_root_visits_device", "kv_root_moves", "kv_root_moves_device", "kv_root_targets", "kv_root_targets_device", "kv_records_device", "kv_sync", "kv_reset_records", "kv_destroy",
             "kv_search", "kv_sizeof_search_result", "kv_search_advance", "kv_search_continue", "kv_search_tree_size",
             "kv_dev_valid_moves", "kv_dev_make_move", "kv_dev_set_starts", "kv_dev_attacks", "kv_host_attacks", "kv_dev_dirichlet", "kv_dev_py_random", "kv_host_libm", "kv_dev_eval_cache",
             "kv_dev_wino88i", "kv_dev_wino88i32_out", "kv_dev_wino88r_out", "kv_dev_tower_front", "kv_dev_tower_back",

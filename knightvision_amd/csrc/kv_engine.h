@@ -67,6 +67,10 @@ struct Ctr {
     unsigned long long roots_carried;  // reuse_tree: committed plies whose root was a carried tree
     int arena_n[2];  // arena: this ply's active slots whose mover plays on net A / net B (k_arena_split)
     unsigned long long plies_fast;  // fast_sims: committed plies searched to the fast target (the rest are full)
+    // forced_k: accepted descents at whose root an edge was forced, and the visits the committed plies' targets
+    // lost to the pruning, sum of (S - sum T); both counted at the move choice
+    unsigned long long forced_descents;
+    unsigned long long visits_pruned;
 };
 
 struct DevCfg {
@@ -172,7 +176,17 @@ struct Tree {  // per-slot SoA edge pools + node records, slot i at i*ecap / i*n
     // idle, or a fast ply whose carried root already holds its target
     int* rem;
     int* tgt;  // fast_sims only (else NULL) [slot]: the visit target of the ply k_mcts_root built, sims or fast_sims
+    // kv_config.forced_k (DESIGN.md "Forced playouts and policy target pruning"; 0: off, the three below unused)
+    float forced_k;
+    int* forced;             // [slot]: this ply's accepted descents whose root had a forced edge (k_mcts_choose zeroes it)
+    uint16_t* root_targets;  // optional [record_cap][MAXM]: the pruned counts T beside root_visits, 0xffff padded
 };
+
+// kv_config.forced_k, the forced rule at the root: an edge with n > 0 visits (in-flight descents counting) is forced
+// while n * n < (k * P) * S, S the root's visit sum as the descent sees it. fp32, no contraction, no sqrtf.
+__device__ inline bool forced_edge(float k, float P, int n, int S) {
+    return n > 0 && (float)n * (float)n < (k * P) * (float)S;
+}
 
 // ---- position search (kv_search.hip): per-tree state, per-(tree, j) descents of the running sim-step ----
 enum : int { SR_SEARCHED = 0, SR_CHECKMATED = 1, SR_STALEMATE = 2, SR_DRAW = 3 };

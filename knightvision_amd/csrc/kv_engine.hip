@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <vector>
 
 #include "kv_common.h"
@@ -877,6 +878,14 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
                "kv_create: full_q16 %d out of range [1, 65536] (65536: every ply full)", cfg->full_q16);
     KV_REQUIRE(cfg->fast_sims == 0 || cfg->arena == 0, KV_EINVAL,
                "kv_create: fast_sims %d with arena 1: a match measures strength at the full search", cfg->fast_sims);
+    KV_REQUIRE(std::isfinite(cfg->forced_k) && cfg->forced_k >= 0.f && cfg->forced_k <= 16.f, KV_EINVAL,
+               "kv_create: forced_k %g out of range: 0 (off) or 0 < forced_k <= 16", (double)cfg->forced_k);
+    KV_REQUIRE(!(cfg->forced_k > 0.f) || cfg->sims >= 1, KV_EINVAL,
+               "kv_create: forced_k %g with sims 0: forced playouts are PUCT descents and need sims >= 1",
+               (double)cfg->forced_k);
+    KV_REQUIRE(!(cfg->forced_k > 0.f) || cfg->arena == 0, KV_EINVAL,
+               "kv_create: forced_k %g with arena 1: a match measures strength at the plain search",
+               (double)cfg->forced_k);
     KV_REQUIRE(cfg->sample_plies >= -1, KV_EINVAL,
                "kv_create: sample_plies %d must be 0 (every ply drawn), k > 0 (first maximum from ply k on) or -1 "
                "(first maximum on every ply)", cfg->sample_plies);
@@ -987,6 +996,13 @@ int kv_create(const kv_config* cfg, kv_engine** out) {
         if (cfg->fast_sims > 0) {
             ALLOC(t.tgt, S * sizeof(int));
             (void)hipMemset(t.tgt, 0, S * sizeof(int));
+        }
+        t.forced_k = cfg->forced_k;
+        if (cfg->forced_k > 0.f) {
+            ALLOC(t.forced, S * sizeof(int));
+            (void)hipMemset(t.forced, 0, S * sizeof(int));
+            if (cfg->keep_root_visits)
+                ALLOC(t.root_targets, (size_t)e->cfg.record_cap * kv::MAXM * sizeof(uint16_t));
         }
         if (e->leaves > 1) {
             kv::SearchWs& w = e->lw;
@@ -2138,6 +2154,8 @@ int kv_stats_get(kv_engine* e, kv_stats* out) {
     out->leaf_batch_rows = e->mc_rows + e->full_rows;
     out->plies_fast = (int64_t)e->ctr_host->plies_fast;
     out->plies_full = out->plies - out->plies_fast;
+    out->forced_descents = (int64_t)e->ctr_host->forced_descents;
+    out->visits_pruned = (int64_t)e->ctr_host->visits_pruned;
     out->arena_rows[0] = e->arena_rows[0];
     out->arena_rows[1] = e->arena_rows[1];
     kv::CacheCtr cc = {0, 0, 0};
@@ -2151,19 +2169,18 @@ int kv_stats_get(kv_engine* e, kv_stats* out) {
 size_t kv_sizeof_config(void) { return sizeof(kv_config); }
 size_t kv_sizeof_stats(void) { return sizeof(kv_stats); }
 
-int kv_root_visits(kv_engine* e, int32_t* out, size_t cap, size_t* n) {
-    KV_REQUIRE(e && n, KV_EINVAL, "kv_root_visits: NULL argument");
-    KV_REQUIRE(e->tree.root_visits, KV_EINVAL, "kv_root_visits: engine was created without keep_root_visits");
+// kv_root_visits / kv_root_targets: the per-record count rows of `buf` in kv_records' order, -1 padded
+static int root_counts(kv_engine* e, const uint16_t* buf, const char* what, int32_t* out, size_t cap, size_t* n) {
     int rc = eng_counters(e);
     if (rc) return rc;
     const size_t cnt = (size_t)std::min<unsigned long long>(e->ctr_host->rec_count, (unsigned long long)e->cfg.record_cap);
     *n = cnt;
     if (!out) return KV_OK;
-    KV_REQUIRE(cap >= cnt, KV_EINVAL, "kv_root_visits: buffer holds %zu records, need %zu", cap, cnt);
+    KV_REQUIRE(cap >= cnt, KV_EINVAL, "%s: buffer holds %zu records, need %zu", what, cap, cnt);
     std::vector<kv_record> rec(cnt);
     std::vector<uint16_t> vis(cnt * kv::MAXM);
     KV_HIP(hipMemcpy(rec.data(), e->rec, cnt * sizeof(kv_record), hipMemcpyDeviceToHost));
-    KV_HIP(hipMemcpy(vis.data(), e->tree.root_visits, vis.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    KV_HIP(hipMemcpy(vis.data(), buf, vis.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
     std::vector<size_t> ord(cnt);
     for (size_t k = 0; k < cnt; ++k) ord[k] = k;
     std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) {  // kv_records' order
@@ -2175,6 +2192,34 @@ int kv_root_visits(kv_engine* e, int32_t* out, size_t cap, size_t* n) {
             out[k * kv::MAXM + j] = v == 0xffff ? -1 : (int32_t)v;
         }
     return KV_OK;
+}
+
+int kv_root_visits(kv_engine* e, int32_t* out, size_t cap, size_t* n) {
+    KV_REQUIRE(e && n, KV_EINVAL, "kv_root_visits: NULL argument");
+    KV_REQUIRE(e->tree.root_visits, KV_EINVAL, "kv_root_visits: engine was created without keep_root_visits");
+    return root_counts(e, e->tree.root_visits, "kv_root_visits", out, cap, n);
+}
+
+int kv_root_targets(kv_engine* e, int32_t* out, size_t cap, size_t* n) {
+    KV_REQUIRE(e && n, KV_EINVAL, "kv_root_targets: NULL argument");
+    KV_REQUIRE(e->tree.root_targets, KV_EINVAL,
+               "kv_root_targets: engine was created without forced_k > 0 and keep_root_visits");
+    return root_counts(e, e->tree.root_targets, "kv_root_targets", out, cap, n);
+}
+
+int kv_root_targets_device(kv_engine* e, uint16_t* out_dev, size_t cap, size_t* n, void* stream) {
+    KV_REQUIRE(e && n, KV_EINVAL, "kv_root_targets_device: NULL argument");
+    KV_REQUIRE(e->tree.root_targets, KV_EINVAL,
+               "kv_root_targets_device: engine was created without forced_k > 0 and keep_root_visits");
+    int rc = eng_counters(e);
+    if (rc) return rc;
+    const size_t cnt = (size_t)std::min<unsigned long long>(e->ctr_host->rec_count, (unsigned long long)e->cfg.record_cap);
+    *n = cnt;
+    if (!out_dev) return KV_OK;
+    KV_REQUIRE(cap >= cnt, KV_EINVAL, "kv_root_targets_device: buffer holds %zu records, need %zu", cap, cnt);
+    KV_HIP(hipMemcpyAsync(out_dev, e->tree.root_targets, cnt * kv::MAXM * sizeof(uint16_t), hipMemcpyDeviceToDevice,
+                          (hipStream_t)stream));
+    return eng_note_copy(e, (hipStream_t)stream);
 }
 
 int kv_root_visits_device(kv_engine* e, uint16_t* out_dev, size_t cap, size_t* n, void* stream) {
@@ -2243,7 +2288,7 @@ void kv_destroy(kv_engine* e) {
                     e->mc_logits, e->mc_values,
                     t.e_V, e->sw.ss, e->sw.lf, e->sw.paths, e->sw.lboards, e->sw.lmoves, e->sw.lcnt, e->sw.llogits,
                     e->sw.lvalues, e->sw.remaining, e->sw.res, e->s_states, e->s_rboards, e->s_rlogits,
-                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves, t.rem, t.tgt,
+                    e->s_rvalues, e->s_hlogits, e->sw.sess, e->s_edge, t.root_moves, t.rem, t.tgt, t.forced, t.root_targets,
                     e->ar_row_of, e->ar_list[0], e->ar_list[1], e->ar_boards[0], e->ar_boards[1], e->ar_moves[0],
                     e->ar_moves[1], e->ar_cnt[0], e->ar_cnt[1], e->ar_llogits[0], e->ar_llogits[1], e->ar_values[0],
                     e->ar_values[1], e->ar_rlogits[0], e->ar_rlogits[1],

@@ -35,6 +35,10 @@
 // fast_sims (ply_target, kv_engine.h): k_mcts_root_pcr writes it into Tree::tgt and mixes a fast ply's noise in with
 // eps = 0, the REUSE kernels search a slot while its root holds fewer visits than that, and rem is written against
 // the next ply's target (k_mcts_carry, or k_mcts_targets without reuse_tree).
+// With kv_config.forced_k (DESIGN.md "Forced playouts and policy target pruning") a full ply's select takes a root
+// edge that holds fewer visits than its forced count before any PUCT score (forced_edge, kv_engine.h), and
+// k_mcts_choose takes those visits out again where PUCT would not have made them (pruned_count): the move is drawn
+// from the pruned counts T, which go to Tree::root_targets; root_visits, k_mcts_carry and every counter keep the raw N.
 // Tree: structure-of-arrays edge pools per slot in HBM (move u16, P f32, N u16,
 // W f32, child u16 per edge: 14 B; a node's edges start on a 16-edge boundary)
 // and one 16-byte record per node (first edge, edge count; N for the root only:
@@ -156,8 +160,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 
 // one slot's select, by the 64 threads of its workgroup. REUSE (kv_config.reuse_tree): a slot whose root
 // already holds sims visits (carried ones counting; with kv_config.fast_sims the ply's own target, Tree::tgt) is not
-// live: no descent, no leaf
-template <bool REUSE>
+// live: no descent, no leaf. FORCED (kv_config.forced_k > 0, DESIGN.md "Forced playouts and policy target
+// pruning"): on a full ply a root edge under its forced count scores +INFINITY, so the first such edge in list order
+// is taken; the false instances are the kernels without the feature
+template <bool REUSE, bool FORCED = false>
 __device__ inline void mcts_select_slot(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards,
                                         int8_t* nn_boards, Ctr* ctr, int i) {
     __shared__ int8_t bd[64];
@@ -177,6 +183,7 @@ __device__ inline void mcts_select_slot(const DevCfg& cfg, const Tree& t, const 
     const size_t eb = (size_t)i * t.ecap, nb = (size_t)i * t.ncap;
     int* path = t.path + nb;
     int node = 0, depth = 0, leaf = -1, parent_n = 0;
+    const bool force = FORCED && (t.tgt == nullptr || t.tgt[i] == cfg.sims);  // a fast ply has no forcing
     for (;;) {
         const NodeRec nd = t.node[nb + node];
         const int first = nd.first, cnt = nd.cnt;
@@ -187,13 +194,15 @@ __device__ inline void mcts_select_slot(const DevCfg& cfg, const Tree& t, const 
         int bi = 0x7fffffff;
         for (int j = lane; j < cnt; j += 64) {
             const size_t e = eb + first + j;
-            const float sc = puct(t.c_puct, t.e_P[e], sq, t.e_N[e], t.e_W[e]);
+            float sc = puct(t.c_puct, t.e_P[e], sq, t.e_N[e], t.e_W[e]);
+            if (FORCED && force && node == 0 && forced_edge(t.forced_k, t.e_P[e], t.e_N[e], nd.N - 1)) sc = INFINITY;
             if (sc > best) {  // lanes see their edges in increasing j: strict > keeps the first
                 best = sc;
                 bi = j;
             }
         }
         wave_argmax_first(best, bi);
+        if (FORCED && force && node == 0 && lane == 0 && best == INFINITY) t.forced[i] += 1;
         const int e = first + bi;
         if (lane == 0) {
             path[depth] = e;
@@ -325,10 +334,11 @@ __device__ inline void mcts_backup_slot(const DevCfg& cfg, const Tree& t, const 
     }
 }
 
-template <bool REUSE>
+template <bool REUSE, bool FORCED>
 __global__ __launch_bounds__(64) void k_mcts_select(DevCfg cfg, Tree t, const Slot* slots, const int8_t* boards,
                                                     int8_t* nn_boards, Ctr* ctr, int slot0, const int* list) {
-    mcts_select_slot<REUSE>(cfg, t, slots, boards, nn_boards, ctr, list ? list[blockIdx.x] : slot0 + blockIdx.x);
+    mcts_select_slot<REUSE, FORCED>(cfg, t, slots, boards, nn_boards, ctr,
+                                    list ? list[blockIdx.x] : slot0 + blockIdx.x);
 }
 
 template <bool REUSE>
@@ -342,7 +352,7 @@ __global__ __launch_bounds__(64) void k_mcts_backup(DevCfg cfg, Tree t, const Sl
 // launch (a slot's next descent depends only on its own tree): one kernel
 // boundary less per sim-step. The barrier orders thread 0's tree writes
 // before the descent reads them (workgroup scope).
-template <bool REUSE>
+template <bool REUSE, bool FORCED>
 __global__ __launch_bounds__(64) void k_mcts_backup_select(DevCfg cfg, Tree t, const Slot* slots,
                                                            const int8_t* boards, const float* logits,
                                                            const float* values, float* probs, int8_t* nn_boards,
@@ -350,21 +360,77 @@ __global__ __launch_bounds__(64) void k_mcts_backup_select(DevCfg cfg, Tree t, c
     const int i = list ? list[blockIdx.x] : slot0 + blockIdx.x;  // (uniform over the workgroup)
     mcts_backup_slot<REUSE>(cfg, t, slots, logits, values, probs, ctr, i);
     __syncthreads();
-    mcts_select_slot<REUSE>(cfg, t, slots, boards, nn_boards, ctr, i);
+    mcts_select_slot<REUSE, FORCED>(cfg, t, slots, boards, nn_boards, ctr, i);
 }
 
+// kv_config.forced_k, policy target pruning (DESIGN.md "Forced playouts and policy target pruning"): the pruned
+// count T of root edge j of a full ply, given the first maximum b of the raw counts and its PUCT score `best`.
+// From N visits, at most f times (f the forced count: the smallest m for which m * m < (k * P) * S fails, capped
+// at N) one visit is taken off while the edge, at its fixed q = W / N and one visit fewer, still scores below
+// `best`; what is left of a pruned edge at 1 goes to 0. puct()'s operation order, fp32, no contraction.
+__device__ inline int pruned_count(float k, float c_puct, float P, float sq, int N, float W, int S, float best) {
+    if (N <= 0) return 0;
+    const float thr = (k * P) * (float)S;
+    int f = 0;
+    while (f < N && (float)f * (float)f < thr) ++f;
+    const float q = W / (float)N;
+    int tv = N;
+    for (int r = 0; r < f; ++r) {
+        const float sc = q + c_puct * P * sq / (float)(1 + (tv - 1));
+        if (!(sc < best)) break;
+        tv -= 1;
+    }
+    if (tv < N && tv == 1) tv = 0;
+    return tv;
+}
+
+// FORCED (kv_config.forced_k > 0): the move is chosen from the pruned counts T, which also go to Tree::root_targets;
+// the false instance is the kernel without the feature
+template <bool FORCED>
 __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* slots, int8_t* boards,
                                                     uint32_t* py_mt, kv_record* rec, int8_t* last_board, Ctr* ctr) {
     __shared__ double vals[MAXM];
     __shared__ double cum[MAXM];
     __shared__ int s_pick;
+    __shared__ uint16_t s_T[FORCED ? MAXM : 1];
     const int i = blockIdx.x, lane = threadIdx.x;
     Slot s = slots[i];
     if (s.status != ST_ACTIVE) return;
     const MctsSlot m = t.ms[i];
     const size_t eb = (size_t)i * t.ecap, nb = (size_t)i * t.ncap;
     const int n = t.node[nb].cnt;
-    for (int j = lane; j < n; j += 64) vals[j] = (double)t.e_N[eb + j];
+    int pruned = 0;
+    if (FORCED) {
+        const bool full = t.tgt == nullptr || t.tgt[i] == cfg.sims;  // a fast ply: T = N
+        float top = -INFINITY;
+        int b = 0x7fffffff, S = 0;
+        for (int j = lane; j < n; j += 64) {
+            const int N = t.e_N[eb + j];
+            S += N;
+            if ((float)N > top) {  // (counts are below 2^16: exact as floats)
+                top = (float)N;
+                b = j;
+            }
+        }
+        wave_argmax_first(top, b);
+#pragma unroll
+        for (int w = 32; w >= 1; w >>= 1) S += __shfl_xor(S, w);
+        const float sq = t.sqrt_tab[t.node[nb].N];
+        const float best = n > 0 ? puct(t.c_puct, t.e_P[eb + b], sq, t.e_N[eb + b], t.e_W[eb + b]) : 0.f;
+        for (int j = lane; j < n; j += 64) {
+            const int N = t.e_N[eb + j];
+            const int T = !full || j == b
+                              ? N
+                              : pruned_count(t.forced_k, t.c_puct, t.e_P[eb + j], sq, N, t.e_W[eb + j], S, best);
+            s_T[j] = (uint16_t)T;
+            vals[j] = (double)T;
+            pruned += N - T;
+        }
+#pragma unroll
+        for (int w = 32; w >= 1; w >>= 1) pruned += __shfl_xor(pruned, w);
+    } else {
+        for (int j = lane; j < n; j += 64) vals[j] = (double)t.e_N[eb + j];
+    }
     __syncthreads();
     if (lane == 0) {
         if (cfg.sample_plies != 0 && (cfg.sample_plies < 0 || s.ply >= cfg.sample_plies)) {
@@ -393,6 +459,12 @@ __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* sl
             atomicAdd(&ctr->sims, (unsigned long long)(cfg.sims - kept));
         }
         atomicAdd(&ctr->nn_rows, (unsigned long long)m.pad[1]);
+        if (FORCED) {
+            const int forced = t.forced[i];
+            t.forced[i] = 0;
+            if (forced) atomicAdd(&ctr->forced_descents, (unsigned long long)forced);
+            if (pruned) atomicAdd(&ctr->visits_pruned, (unsigned long long)pruned);
+        }
         if (t.rem != nullptr) {
             t.ms[i].pad[3] = s_pick;  // the played root edge, for k_mcts_carry
             if (m.pad[2] != 0) {
@@ -412,6 +484,10 @@ __global__ __launch_bounds__(64) void k_mcts_choose(DevCfg cfg, Tree t, Slot* sl
         if (t.root_moves) {
             uint16_t* rm = t.root_moves + (size_t)ridx * MAXM;
             for (int j = lane; j < MAXM; j += 64) rm[j] = j < n ? t.e_move[eb + j] : (uint16_t)0xffff;
+        }
+        if (FORCED && t.root_targets) {
+            uint16_t* rt = t.root_targets + (size_t)ridx * MAXM;
+            for (int j = lane; j < MAXM; j += 64) rt[j] = j < n ? s_T[j] : (uint16_t)0xffff;
         }
     }
     if (lane == 0) slots[i] = s;
@@ -520,12 +596,10 @@ int mcts_root(const DevCfg& cfg, const Tree& t, Slot* slots, const uint16_t* mov
 
 int mcts_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, int8_t* nn_boards,
                 Ctr* ctr, hipStream_t st, int slot0, int count, bool reuse, const int* list) {
-    if (reuse)
-        hipLaunchKernelGGL(k_mcts_select<true>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, nn_boards, ctr,
-                           slot0, list);
-    else
-        hipLaunchKernelGGL(k_mcts_select<false>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, nn_boards, ctr,
-                           slot0, list);
+    // (kv_config.forced_k > 0: the FORCED instances; 0 launches the kernels without the feature)
+    const auto k = t.forced_k > 0.f ? (reuse ? k_mcts_select<true, true> : k_mcts_select<false, true>)
+                                    : (reuse ? k_mcts_select<true, false> : k_mcts_select<false, false>);
+    hipLaunchKernelGGL(k, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, nn_boards, ctr, slot0, list);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
@@ -545,20 +619,18 @@ int mcts_backup(const DevCfg& cfg, const Tree& t, const Slot* slots, const float
 int mcts_backup_select(const DevCfg& cfg, const Tree& t, const Slot* slots, const int8_t* boards, const float* logits,
                        const float* values, float* probs, int8_t* nn_boards, Ctr* ctr, hipStream_t st, int slot0,
                        int count, bool reuse, const int* list) {
-    if (reuse)
-        hipLaunchKernelGGL(k_mcts_backup_select<true>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, logits,
-                           values, probs, nn_boards, ctr, slot0, list);
-    else
-        hipLaunchKernelGGL(k_mcts_backup_select<false>, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, logits,
-                           values, probs, nn_boards, ctr, slot0, list);
+    const auto k = t.forced_k > 0.f ? (reuse ? k_mcts_backup_select<true, true> : k_mcts_backup_select<false, true>)
+                                    : (reuse ? k_mcts_backup_select<true, false> : k_mcts_backup_select<false, false>);
+    hipLaunchKernelGGL(k, dim3(count), dim3(64), 0, st, cfg, t, slots, boards, logits, values, probs, nn_boards, ctr,
+                       slot0, list);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
 
 int mcts_choose(const DevCfg& cfg, const Tree& t, Slot* slots, int8_t* boards, uint32_t* py_mt, kv_record* rec,
                 int8_t* last_board, Ctr* ctr, hipStream_t st) {
-    hipLaunchKernelGGL(k_mcts_choose, dim3(cfg.slots), dim3(64), 0, st, cfg, t, slots, boards, py_mt, rec,
-                       last_board, ctr);
+    hipLaunchKernelGGL(t.forced_k > 0.f ? k_mcts_choose<true> : k_mcts_choose<false>, dim3(cfg.slots), dim3(64), 0, st,
+                       cfg, t, slots, boards, py_mt, rec, last_board, ctr);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }

@@ -96,11 +96,14 @@ __global__ __launch_bounds__(64) void k_search_load(Tree t, SearchWs w, Slot* sl
 // one tree's descents of a sim-step, by the 64 threads of its workgroup. SP: the tree is a self-play slot's
 // (kv_config.leaves > 1, k_leaves_* below): it is searched while the slot is active and its root holds fewer than
 // sims backups, and ss.done is written for the step's compaction (sims for a slot that takes no descent)
-// (kv_config.fast_sims: fewer than the ply's own target, Tree::tgt)
-template <bool HASV, bool SP = false>
+// (kv_config.fast_sims: fewer than the ply's own target, Tree::tgt). FORCED (SP trees with kv_config.forced_k > 0):
+// kv_mcts.hip's forced rule at node 0 of a full ply, on N + V and the root's visit sum nd.N + vroot - 1
+template <bool HASV, bool SP = false, bool FORCED = false>
 __device__ inline void search_select_tree(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards,
                                           Ctr* ctr, int sims, int L, int i) {
     if (SP && t.tgt != nullptr) sims = t.tgt[i];
+    const bool force = FORCED && sims == t.sims;  // a fast ply has no forcing
+    int forced = 0;
     __shared__ int8_t root_bd[64];
     __shared__ int8_t bd[64];
     __shared__ int s_meta[8];                // wtm wkr wkc bkr bkc flags ep
@@ -131,6 +134,7 @@ __device__ inline void search_select_tree(const Tree& t, const SearchWs& w, cons
             const size_t row = row0 + j;
             int* path = w.paths + row * t.ncap;
             int node = 0, depth = 0, leaf = -1, parent_n = 0;
+            bool by_force = false;
             for (;;) {
                 const NodeRec nd = t.node[nb + node];
                 const int first = nd.first, cnt = nd.cnt;
@@ -139,14 +143,18 @@ __device__ inline void search_select_tree(const Tree& t, const SearchWs& w, cons
                 int bi = 0x7fffffff;
                 for (int k = lane; k < cnt; k += 64) {
                     const size_t e = eb + first + k;
-                    const float sc = HASV ? puct_inflight(t.c_puct, t.e_P[e], sq, t.e_N[e], t.e_V[e], t.e_W[e])
-                                          : puct(t.c_puct, t.e_P[e], sq, t.e_N[e], t.e_W[e]);
+                    float sc = HASV ? puct_inflight(t.c_puct, t.e_P[e], sq, t.e_N[e], t.e_V[e], t.e_W[e])
+                                    : puct(t.c_puct, t.e_P[e], sq, t.e_N[e], t.e_W[e]);
+                    if (FORCED && force && node == 0 &&
+                        forced_edge(t.forced_k, t.e_P[e], t.e_N[e] + t.e_V[e], nd.N + vroot - 1))
+                        sc = INFINITY;
                     if (sc > best) {  // lanes see their edges in increasing k: strict > keeps the first
                         best = sc;
                         bi = k;
                     }
                 }
                 wave_argmax_first(best, bi);
+                if (FORCED && force && node == 0) by_force = best == INFINITY;
                 if (bi >= cnt) bi = 0;  // no score compared greater (NaN priors): stay inside the node's edges
                 const int e = first + bi;
                 if (lane == 0) {
@@ -193,6 +201,7 @@ __device__ inline void search_select_tree(const Tree& t, const SearchWs& w, cons
             if (HASV)  // accepted: one more descent in flight on every edge of the path
                 for (int d = lane; d < depth; d += 64) t.e_V[eb + path[d]] += 1;
             vroot += 1;
+            if (FORCED && by_force) forced += 1;  // (an accepted descent: a dropped one counts nowhere)
             if (lane == 0) {
                 w.lf[row] = lf;
                 w.lcnt[row] = lf.pending ? lf.n : 0;
@@ -207,6 +216,7 @@ __device__ inline void search_select_tree(const Tree& t, const SearchWs& w, cons
         ss.accepted = accepted;
         ss.vroot = accepted;
         w.ss[i] = ss;
+        if (FORCED && forced) t.forced[i] += forced;  // (k_mcts_choose adds the ply's count to Ctr::forced_descents)
     }
 }
 
@@ -388,9 +398,10 @@ __global__ __launch_bounds__(64) void k_search_result(Tree t, SearchWs w, const 
 // in self-play"): the sim-step above on the slots' own trees, after k_mcts_root. One wavefront per slot; the leaf
 // of descent j of slot i is row i * L + j of w. e_V is all 0 between sim-steps (every accepted descent's increments
 // are taken back by its backup, an expansion zeroes its edges'), so the roots k_mcts_root builds need no reset.
+template <bool FORCED>
 __global__ __launch_bounds__(64) void k_leaves_select(Tree t, SearchWs w, const Slot* slots, const int8_t* boards,
                                                       Ctr* ctr, int sims, int L) {
-    search_select_tree<true, true>(t, w, slots, boards, ctr, sims, L, blockIdx.x);
+    search_select_tree<true, true, FORCED>(t, w, slots, boards, ctr, sims, L, blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void k_leaves_backup(Tree t, SearchWs w, Ctr* ctr, int sims, int L) {
@@ -398,16 +409,19 @@ __global__ __launch_bounds__(64) void k_leaves_backup(Tree t, SearchWs w, Ctr* c
 }
 
 // backup of sim-step k and select of sim-step k + 1 of the same slot in one launch (k_mcts_backup_select)
+template <bool FORCED>
 __global__ __launch_bounds__(64) void k_leaves_backup_select(Tree t, SearchWs w, const Slot* slots,
                                                              const int8_t* boards, Ctr* ctr, int sims, int L) {
     search_backup_tree<true, true>(t, w, ctr, sims, L, blockIdx.x);
     __syncthreads();
-    search_select_tree<true, true>(t, w, slots, boards, ctr, sims, L, blockIdx.x);
+    search_select_tree<true, true, FORCED>(t, w, slots, boards, ctr, sims, L, blockIdx.x);
 }
 
 int leaves_select(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr, int sims,
                   int n, int L, hipStream_t st) {
-    hipLaunchKernelGGL(k_leaves_select, dim3(n), dim3(64), 0, st, t, w, slots, boards, ctr, sims, L);
+    // (kv_config.forced_k > 0: the FORCED instances; 0 launches the kernels without the feature)
+    hipLaunchKernelGGL(t.forced_k > 0.f ? k_leaves_select<true> : k_leaves_select<false>, dim3(n), dim3(64), 0, st, t,
+                       w, slots, boards, ctr, sims, L);
     KV_HIP(hipGetLastError());
     return KV_OK;
 }
@@ -415,7 +429,8 @@ int leaves_select(const Tree& t, const SearchWs& w, const Slot* slots, const int
 int leaves_backup(const Tree& t, const SearchWs& w, const Slot* slots, const int8_t* boards, Ctr* ctr, int sims,
                   int n, int L, bool select, hipStream_t st) {
     if (select)
-        hipLaunchKernelGGL(k_leaves_backup_select, dim3(n), dim3(64), 0, st, t, w, slots, boards, ctr, sims, L);
+        hipLaunchKernelGGL(t.forced_k > 0.f ? k_leaves_backup_select<true> : k_leaves_backup_select<false>, dim3(n),
+                           dim3(64), 0, st, t, w, slots, boards, ctr, sims, L);
     else
         hipLaunchKernelGGL(k_leaves_backup, dim3(n), dim3(64), 0, st, t, w, ctr, sims, L);
     KV_HIP(hipGetLastError());

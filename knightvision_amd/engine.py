@@ -49,7 +49,8 @@ class SelfPlayEngine:
                  batch=16, eps=0.25, alpha=0.3, sims=0, c_puct=1.5, eval_mode=EVAL_FAITHFUL, record_cap=None,
                  recycle=True, device=0, game_id_base=0, game_id_stride=1, precision="fp32",
                  algo="auto", tree_edge_cap=0, keep_root_visits=False, keep_root_moves=False, reuse_tree=False,
-                 sim_groups=0, opponent=None, sample_plies=0, leaves=0, eval_cache=0, fast_sims=0, full_prob=0.25):
+                 sim_groups=0, opponent=None, sample_plies=0, leaves=0, eval_cache=0, fast_sims=0, full_prob=0.25,
+                 forced_k=0.0):
         """opponent (MCTS, sims >= 1): a second weight set makes the engine an arena (kv_config.arena): `weights`
         is player A, `opponent` player B, A plays white in the games with an even global id, and every ply is
         searched on the net of the side to move; games()["outcome"] stays white-perspective (arena.summarize
@@ -73,7 +74,12 @@ class SelfPlayEngine:
         randomization -- each ply is searched to `sims` root visits with probability full_prob and to fast_sims
         otherwise (a pure function of seed, game id and ply; full_q16 = round(full_prob * 65536) clipped to
         [1, 65536]). A fast ply's record has pad bit 0 set (fast_mask): it gives a value target and no policy
-        target. stats() reports plies_full / plies_fast. Not with an opponent."""
+        target. stats() reports plies_full / plies_fast. Not with an opponent.
+        forced_k (MCTS self-play; kv_config.forced_k): 0 off; 0 < forced_k <= 16 (KataGo: 2) turns on forced playouts
+        and policy target pruning -- on a full ply a visited root move is searched at least sqrt(forced_k * P * visits)
+        times, and at the move choice the forced visits PUCT would not have made are taken out again: the move is drawn
+        from the pruned counts, which root_targets() returns (with keep_root_visits), while root_visits() keeps the
+        raw ones. stats() reports forced_descents / visits_pruned. Not with an opponent."""
         L = _lib.lib()
         keep = 2 if keep_root_moves else (1 if keep_root_visits else 0)  # the move words imply the visits
         if record_cap is None:
@@ -92,7 +98,7 @@ class SelfPlayEngine:
                           tree_edge_cap=int(tree_edge_cap), keep_root_visits=keep, reuse_tree=int(reuse_tree),
                           sim_groups=int(sim_groups), arena=0 if opponent is None else 1,
                           sample_plies=int(sample_plies), leaves=int(leaves), eval_cache=int(eval_cache),
-                          fast_sims=int(fast_sims), full_q16=full_q16)
+                          fast_sims=int(fast_sims), full_q16=full_q16, forced_k=float(forced_k))
         h = C.c_void_p()
         _lib.check(L.kv_create(C.byref(cfg), C.byref(h)), "kv_create")
         self.h = h
@@ -186,6 +192,33 @@ class SelfPlayEngine:
         if n.value:
             _lib.check(L.kv_root_visits(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)),
                        "kv_root_visits")
+        return out
+
+    def root_targets(self) -> np.ndarray:
+        """The pruned root counts T (the policy targets of forced_k > 0) [records, MAXM] (-1 padded), rows in
+        records() order, root_visits()'s layout (needs forced_k > 0 and keep_root_visits=True)."""
+        L = _lib.lib()
+        n = C.c_size_t()
+        _lib.check(L.kv_root_targets(self.h, None, 0, C.byref(n)), "kv_root_targets")
+        out = np.zeros((n.value, _lib.MAXM), dtype=np.int32)
+        if n.value:
+            _lib.check(L.kv_root_targets(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n)),
+                       "kv_root_targets")
+        return out
+
+    def root_targets_device(self):
+        """The same counts as a uint8 CUDA tensor [n, MAXM * 2] (uint16, 0xffff padded), row k belonging to row k
+        of records_device() and of root_visits_device()."""
+        import torch
+        L = _lib.lib()
+        n = C.c_size_t()
+        _lib.check(L.kv_root_targets_device(self.h, None, 0, C.byref(n), None), "kv_root_targets_device")
+        dev = torch.device("cuda", self.cfg.device)
+        out = torch.empty((n.value, _lib.MAXM * 2), dtype=torch.uint8, device=dev)
+        if n.value:
+            st = torch.cuda.current_stream(dev).cuda_stream
+            _lib.check(L.kv_root_targets_device(self.h, C.c_void_p(out.data_ptr()), n.value, C.byref(n),
+                                                C.c_void_p(st)), "kv_root_targets_device")
         return out
 
     def root_moves(self) -> np.ndarray:

@@ -37,6 +37,11 @@ fast_sims. Every record gives a value target; in "visits" mode only the full
 plies give a policy target (PolicyTargets.w is 0 on the fast ones). "move"
 mode trains on every record as before.
 
+forced_k > 0 (no reference counterpart; MCTS self-play only) turns on forced
+playouts and policy target pruning (kv_config.forced_k, DESIGN.md "Forced
+playouts and policy target pruning"): in "visits" mode the policy targets are
+the pruned root counts (engine.root_targets) instead of the raw visit counts.
+
 arena_games > 0 (no reference counterpart; the reference evaluates against
 Stockfish here, learn.py:204-206): after an iteration's update the new weights
 play a match against the weights the iteration started from (arena.py,
@@ -81,7 +86,7 @@ def _dist():
 
 def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_moves=None, slots=256,
                    precision="fp32", policy_targets=False, reuse_tree=False, leaves=0, eval_cache=0, fast_sims=0,
-                   full_prob=0.25):
+                   full_prob=0.25, forced_k=0.0):
     """This rank's share of one iteration's games, played by the HIP engine with
     the model's current weights. Returns (records, games) numpy arrays; with
     policy_targets (MCTS runs) also the root visit counts and root move words of
@@ -92,7 +97,9 @@ def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_m
     per game and sim-step (kv_config.leaves); eval_cache (leaves >= 2): entries of the engine's exact leaf-row cache
     (kv_config.eval_cache; 0: off), which changes no record. fast_sims > 0 (0 < fast_sims < sims): playout cap
     randomization (kv_config.fast_sims) -- a ply is searched to sims visits with probability full_prob and to
-    fast_sims otherwise; the records of fast plies carry pad bit 0 (engine.fast_mask)."""
+    fast_sims otherwise; the records of fast plies carry pad bit 0 (engine.fast_mask). forced_k > 0: forced playouts
+    and policy target pruning (kv_config.forced_k); with policy_targets the third array is then the pruned counts
+    (engine.root_targets) in place of the raw visit counts, the same layout."""
     dist, rank, world = _dist()
     dev = torch.device(device)
     ids = list(range(rank, n_games, world))
@@ -107,12 +114,14 @@ def selfplay_shard(model, n_games: int, iteration: int, device, *, sims=0, max_m
                         game_id_base=base, game_id_stride=world, device=dev.index or 0,
                         precision=precision, eval_mode=batched_eval_mode() if sims == 0 else 0,
                         keep_root_moves=bool(policy_targets), reuse_tree=bool(reuse_tree), leaves=int(leaves),
-                        eval_cache=int(eval_cache), fast_sims=int(fast_sims), full_prob=float(full_prob)) as eng:
+                        eval_cache=int(eval_cache), fast_sims=int(fast_sims), full_prob=float(full_prob),
+                        forced_k=float(forced_k)) as eng:
         eng.run()
         selfplay_shard.last_calibration = eng.calibration()  # the conv paths these weights ran on
         selfplay_shard.last_stats = eng.stats()
         if policy_targets:
-            return eng.records(), eng.games(), eng.root_visits().astype("uint16"), eng.root_moves()
+            counts = eng.root_targets() if forced_k > 0 else eng.root_visits()
+            return eng.records(), eng.games(), counts.astype("uint16"), eng.root_moves()
         return eng.records(), eng.games()
 
 
@@ -318,7 +327,7 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
                        policy_target: str = "move", reuse_tree: bool = False, arena_games: int = 0,
                        arena_sims: int | None = None, leaves: int = 0, arena_leaves: int | None = None,
                        eval_cache: int = 0, arena_eval_cache: int | None = None, fast_sims: int = 0,
-                       full_prob: float = 0.25):
+                       full_prob: float = 0.25, forced_k: float = 0.0):
     """Run the loop (learn.py reinforcement_loop :152-209); returns per-iteration statistics.
     `model` is a knightvision_amd.model.ChessNet (same parameters as ai/model.py) on `device`.
     `games_path`: the reference's JSONL dataset (ChessPGNDataset, :162) the self-play records extend --
@@ -344,7 +353,10 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
     `fast_sims`. The statistics gain plies_full / plies_fast. With policy_target="visits" only the full plies'
     visit distributions train the policy (PolicyTargets.w, train.batch_loss); every record trains the value
     head. policy_target="move" trains on every record, fast plies included, as before. The matches
-    (`arena_games`) always search every ply to `arena_sims`."""
+    (`arena_games`) always search every ply to `arena_sims`.
+    `forced_k` > 0 (no reference counterpart): forced playouts and policy target pruning in self-play
+    (kv_config.forced_k; KataGo: 2). With policy_target="visits" the policy trains on the pruned root counts; the
+    statistics gain forced_descents / visits_pruned. The matches always run the plain search."""
     if policy_target not in ("move", "visits"):
         raise ValueError(f"reinforcement_loop: policy_target {policy_target!r}: 'move' or 'visits'")
     if arena_games > 0 and (arena_sims if arena_sims is not None else sims) <= 0:
@@ -397,12 +409,12 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
             recs, games, *pi = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves,
                                               slots=slots, policy_targets=True, reuse_tree=reuse_tree,
                                               leaves=leaves, eval_cache=eval_cache, fast_sims=fast_sims,
-                                              full_prob=full_prob)
+                                              full_prob=full_prob, forced_k=forced_k)
             pi = None if recs is None else tuple(pi)
         else:
             recs, games = selfplay_shard(model, games_per_iter, it, dev, sims=sims, max_moves=max_moves, slots=slots,
                                          reuse_tree=reuse_tree, leaves=leaves, eval_cache=eval_cache,
-                                         fast_sims=fast_sims, full_prob=full_prob)
+                                         fast_sims=fast_sims, full_prob=full_prob, forced_k=forced_k)
         st["selfplay_s"] = time.perf_counter() - t0
         cal = getattr(selfplay_shard, "last_calibration", None)
         if cal is not None:  # fp32 AUTO: the self-play network's conv path for this iteration's weights
@@ -414,7 +426,8 @@ def reinforcement_loop(model, iterations: int, games_per_iter: int, device, *, e
         if es is not None:  # this rank's engine: plies and MCTS simulations (the throughput a path flip moves)
             st.update(plies=int(es["plies"]), sims=int(es["sims"]), sims_kept=int(es["sims_kept"]),
                       leaf_batch_rows=int(es["leaf_batch_rows"]), sim_steps=int(es["sim_steps"]),
-                      plies_full=int(es["plies_full"]), plies_fast=int(es["plies_fast"]))
+                      plies_full=int(es["plies_full"]), plies_fast=int(es["plies_fast"]),
+                      forced_descents=int(es["forced_descents"]), visits_pruned=int(es["visits_pruned"]))
         model.train()
         data = extend_dataset(data, recs, games, dev, pi=pi, policy_targets=True, weighted=fast_sims > 0) if visits \
             else extend_dataset(data, recs, games, dev)
